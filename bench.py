@@ -1,7 +1,17 @@
 """bench.py — cell-updates/s of the MI355X Game of Life engine (libgolhip.so).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 65536|16384|262144|5120]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline `value` needs and no more: set up, the
+parity step and warmup, the K timed steps, the line.  `--full` adds every
+other measurement to the same line: `cpu_baseline`, the `configs3` block of
+the default workload, and for --workload 5120 / 512 the fixture parity run,
+`events_off`, the K5 `roofline` against the host-link probes, `end_to_end`
+and `buffered_1000`.  `--dump-outputs DIR` writes what the last timed step
+left its caller as DIR/<name>.npy (float32 / float64; dump_board,
+dump_events, run_main): the same arrays for the same arguments, run to run.
 
 A "step" is one run of the workload's BASELINE config over the whole board:
 its turns (configs[2]: 1,000) of the synthetic torus, run as fused launches.
@@ -26,10 +36,11 @@ summed over ranks) and alive count must equal tests/golden/fullsize.json (the
 oracle's answer, tests/golden/make_fullsize.py).  The JSON line carries
 "parity": true/false and the run exits 1 after printing on a mismatch.
 
-Warmup: W untimed steps (at least 1, the parity step), then more untimed steps
-until --warmup-seconds have passed.  Rank 0 prints ONE JSON line; `roofline`
+Warmup: untimed steps until --warmup-seconds have passed, then, from the
+freshly filled board again, W untimed steps (at least 1, the parity step).
+Rank 0 prints ONE JSON line; `roofline`
 is measured live on the step kernels with HIP events on the engine's stream
-(see roofline_block); `cpu_baseline` times the oracle's port of the reference
+(see roofline_block); `cpu_baseline` (--full) times the oracle's port of the reference
 worker pool on a bounded sample (rank 0, N = 1 only), with the bit-packed
 OpenMP CPU comparator beside it (`cpu_baseline.fast_cpu`).
 """
@@ -104,7 +115,17 @@ def parse():
     ap.add_argument("--configs3-warmup-seconds", type=float, default=1.0)
     ap.add_argument("--pmc", default=os.path.join(ROOT, "profiles", "pmc_bench.json"),
                     help="rocprofv3 --pmc summary of this bench command (scripts/pmc_bench.py)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: the CPU baselines, the configs[3] "
+                         "block, and for --workload 5120 / 512 the fixture parity run, events off, the K5 kernel "
+                         "time and host-link probes, the end_to_end block and the buffered channel")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                         "(float32 / float64, see dump_board)")
+    a = ap.parse_args()
+    if not a.full:  # a plain run: set up, warm up, the timed steps, the line
+        a.no_cpu_baseline, a.configs3, a.e2e_turns = True, False, 0
+    return a
 
 
 def host_info() -> dict:
@@ -354,9 +375,51 @@ def roofline_block(perf: dict, W: int, rows: int, workload: int, pmc_path: str, 
     return out
 
 
+DUMP_SEED = 0xD0D0
+DUMP_ROW_BYTES = 40 << 20  # sampled board rows of a dump, as float32 cells (the whole dump stays under 64 MB)
+
+
+def dump_arrays(d: str, arrays: dict) -> None:
+    """--dump-outputs: DIR/<name>.npy, float32 or float64 arrays only."""
+    os.makedirs(d, exist_ok=True)
+    for name, arr in arrays.items():
+        arr = np.ascontiguousarray(arr)
+        if arr.dtype not in (np.float32, np.float64):
+            raise TypeError(f"{name}: {arr.dtype}")
+        np.save(os.path.join(d, name + ".npy"), arr)
+
+
+def dump_sample_rows(W: int, H: int) -> np.ndarray:
+    """The board rows a dump holds: rows 0 and H - 1 (the torus seam) and a
+    seeded sample, up to 160 rows and DUMP_ROW_BYTES of float32 cells; the
+    same rows for the same board size, sorted."""
+    n = max(1, min(H, 160, DUMP_ROW_BYTES // (4 * W)))
+    rows = np.random.default_rng(DUMP_SEED).choice(H, n, replace=False)
+    return np.unique(np.concatenate([rows, [0, H - 1]])).astype(np.int64)
+
+
+def dump_board(d: str, board, W: int, H: int, row0: int, nrows: int, digest: int, alive: int, turn: int,
+               suffix: str = "", scalars: bool = True) -> None:
+    """What a caller of the timed path holds after its last step, the board:
+    `board_rows` (sampled rows of this handle as 0/1 float32 cells, whole
+    rows), `board_row_index` (their board rows), and of the whole board
+    `board_digest` (golhip_board_hash summed over ranks, as its high and low
+    32 bits) and `board_alive` (alive count, completed turns)."""
+    mine = [int(r) for r in dump_sample_rows(W, H) if row0 <= r < row0 + nrows]
+    cells = np.empty((len(mine), W), dtype=np.float32)
+    for i, r in enumerate(mine):
+        words = board.snapshot_rows(r - row0, 1)  # cell c of a row: bit c % 32 of word c // 32
+        cells[i] = np.unpackbits(words.view(np.uint8), bitorder="little")[:W]
+    arrays = {"board_rows" + suffix: cells, "board_row_index" + suffix: np.array(mine, dtype=np.float64)}
+    if scalars:
+        arrays["board_digest"] = np.array([digest >> 32, digest & 0xFFFFFFFF], dtype=np.float64)
+        arrays["board_alive"] = np.array([alive, turn], dtype=np.float64)
+    dump_arrays(d, arrays)
+
+
 def events_main(a) -> None:
     """configs[4]: 5120^2 with the full event stream ("GCUPS with
-    events on vs off").  Parity first: the CellFlipped lists of turns 1..50
+    events on vs off").  Parity first (--full): the CellFlipped lists of turns 1..50
     from the fresh board (int32 (x, y) pairs, row-major per turn) must equal
     tests/golden/fullsize.json c4 (per-turn counts + SHA-256 of the pairs).
     Then the board runs untimed to turn 2064 (past the random board's first
@@ -364,7 +427,7 @@ def events_main(a) -> None:
     through golhip_flip_stream with 4-byte cell indices written by the kernel
     into page-locked host memory (golhip_host_alloc), every turn's list
     complete on the host: `value` = W x H x turns / s with events on.
-    `events_off` times the same turns on fused launches (no lists)."""
+    `events_off` (--full) times the same turns on fused launches (no lists)."""
     import hashlib
 
     import torch
@@ -374,34 +437,41 @@ def events_main(a) -> None:
     with open(FULLSIZE) as f:
         rec = c4 = json.load(f)["c4"]
     cap = 32 << 20
-    # parity: turns 1..T of the fixture, pairs
-    T = len(rec["flip_counts"])
-    xy = np.empty((cap, 2), dtype=np.int32)
-    sha, counts = hashlib.sha256(), []
-    with golhip.Board(N, N) as b:
-        b.fill_random(wl["seed"])
-        done = 0
-        while done < T:
-            ent, cnt, k = b.flip_stream(T - done, cap=cap, fmt=golhip.FLIPS_XY, out=xy)
-            sha.update(ent.tobytes())
-            counts += [int(c) for c in cnt]
-            done += k
-    parity = {"turns": T, "flips": sum(counts), "sha256": sha.hexdigest()[:16],
-              "ok": sha.hexdigest() == rec["flips_sha256"] and counts == rec["flip_counts"][:T],
-              "fixture": "tests/golden/fullsize.json c4 turns 1..%d" % T}
+    parity = {"ok": None, "note": "the fixture parity run is part of --full"}
+    if a.full:
+        # parity: turns 1..T of the fixture, pairs
+        T = len(rec["flip_counts"])
+        xy = np.empty((cap, 2), dtype=np.int32)
+        sha, counts = hashlib.sha256(), []
+        with golhip.Board(N, N) as b:
+            b.fill_random(wl["seed"])
+            done = 0
+            while done < T:
+                ent, cnt, k = b.flip_stream(T - done, cap=cap, fmt=golhip.FLIPS_XY, out=xy)
+                sha.update(ent.tobytes())
+                counts += [int(c) for c in cnt]
+                done += k
+        parity = {"turns": T, "flips": sum(counts), "sha256": sha.hexdigest()[:16],
+                  "ok": sha.hexdigest() == rec["flips_sha256"] and counts == rec["flip_counts"][:T],
+                  "fixture": "tests/golden/fullsize.json c4 turns 1..%d" % T}
+        del xy
     idx = golhip.host_array((cap,), np.uint32)
     idx.fill(0)
+    last = {}  # the newest golhip_flip_stream call's entries (a view of idx) and per-turn counts
 
     def stream(b, turns):
-        done, flips = 0, 0
+        done, flips, counts = 0, 0, []
         while done < turns:
             ent, cnt, k = b.flip_stream(turns - done, cap=cap, fmt=golhip.FLIPS_INDEX, out=idx)
             done += k
             flips += len(ent)
+            counts.append(cnt)
+        last.update(ent=ent, counts=counts)
         return flips
 
     res = {}
-    for timed in (False, True):  # turns/s without per-launch HIP events; the K5 kernel time with them
+    # turns/s without per-launch HIP events; --full: the K5 kernel time with them
+    for timed in (False, True) if a.full else (False,):
         with golhip.Board(N, N, timing=timed) as b:
             for kv in a.option:  # A/B runs (the plan's knobs need GOLHIP_TUNING=1)
                 k, v = kv.split("=", 1)
@@ -418,6 +488,9 @@ def events_main(a) -> None:
             dt = time.perf_counter() - t0
             if not timed:
                 res.update(dt=dt, flips=flips)
+                if a.dump_outputs:
+                    dump_events(a.dump_outputs, b, last)
+            if not timed and a.full:
                 # events off: the same turns on fused launches, from the same turn
                 b.fill_random(wl["seed"])
                 b.step(2064 + max(1, a.warmup) * tps)
@@ -427,17 +500,10 @@ def events_main(a) -> None:
                     b.step(tps)
                 b.sync()
                 res["dt_off"] = time.perf_counter() - t1
-            else:
+            elif timed:
                 res["perf"] = b.perf()
                 res["flips_timed"] = flips
-    p = res["perf"]
     turns = tps * a.steps
-    kus = p["flip_kernel_ms"] * 1e3 / max(1, p["flip_launches"])
-    host_b = res["flips_timed"] / max(1, turns) * 4  # K5's entries per launch (4-byte indices, host memory)
-    alg = 2 * N * N / 8 + host_b  # board in + out + entries, per launch
-    link = golhip.host_link_probe(0)  # the link's ceiling for those stores, measured here
-    # ... and at the size of one turn's list, one launch a list (K5's own shape)
-    link_turn = golhip.host_link_probe(0, max(4096, int(host_b) // 16 * 16), 50)
     out = {
         "metric": METRIC, "value": round(N * N * turns / res["dt"] / 1e9, 3), "unit": "GCUPS", "n_gpus": 1,
         "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(res["dt"] / a.steps * 1e3, 4),
@@ -450,6 +516,41 @@ def events_main(a) -> None:
                    "parallelism": "single GPU torus"},
         "events_on": {"turns_per_s": round(turns / res["dt"], 1), "flips_per_s": round(res["flips"] / res["dt"], 1),
                       "flips": res["flips"]},
+    }
+    if a.full:
+        events_full(a, out, res, c4, N, turns)
+    print(json.dumps(out), flush=True)
+    if out["parity"] is False:
+        sys.exit(1)
+
+
+def dump_events(d: str, b, last: dict) -> None:
+    """--workload 5120's outputs of the last timed step: `flip_counts` (the
+    CellFlipped count of each of its turns), `flips_last_turn` (the last
+    turn's list, cell indices y * W + x in list order), and the board after it
+    (`board_words`: every row's bit words, cell c in bit c % 32 of word
+    c // 32; `board_alive`: alive count, completed turns)."""
+    counts = np.concatenate(last["counts"])
+    n = int(counts[-1])
+    ent = np.array(last["ent"][len(last["ent"]) - n:], dtype=np.float64)
+    alive, turn = b.alive_count()
+    dump_arrays(d, {"flip_counts": counts.astype(np.float64), "flips_last_turn": ent,
+                    "board_words": b.snapshot_bits().astype(np.float64),
+                    "board_alive": np.array([alive, turn], dtype=np.float64)})
+
+
+def events_full(a, out: dict, res: dict, c4: dict, N: int, turns: int) -> None:
+    """--full blocks of the configs[4] line: events off, the K5 roofline
+    against the host link measured here, end_to_end, the CPU baselines."""
+    parity = out["parity_check"]
+    p = res["perf"]
+    kus =p["flip_kernel_ms"] * 1e3 / max(1, p["flip_launches"])
+    host_b = res["flips_timed"] / max(1, turns) * 4  # K5's entries per launch (4-byte indices, host memory)
+    alg = 2 * N * N / 8 + host_b  # board in + out + entries, per launch
+    link = golhip.host_link_probe(0)  # the link's ceiling for those stores, measured here
+    # ... and at the size of one turn's list, one launch a list (K5's own shape)
+    link_turn = golhip.host_link_probe(0, max(4096, int(host_b) // 16 * 16), 50)
+    out.update({
         "events_off": {"gcups": round(N * N * turns / res["dt_off"] / 1e9, 3),
                        "turns_per_s": round(turns / res["dt_off"], 1)},
         "roofline": {"bound": "host-link", "achieved": round(host_b / (kus * 1e-6) / 1e9, 2) if kus > 0 else None,
@@ -477,7 +578,7 @@ def events_main(a) -> None:
                              "`avg_launch_ms` count turns): the entries cross the host link into page-locked "
                              "memory; achieved = entry bytes per turn / the turn's device time (HIP events), "
                              "stream_GBps the same bytes over the timed wall clock (host syncs included)"},
-    }
+    })
     try:  # HBM bytes of K5 from the PMC passes of this command (scripts/pmc_bench.sh ... 5120)
         with open(a.pmc) as f:
             rec = json.load(f).get(f"{N}:gol_flip_turn_kernel")
@@ -499,11 +600,8 @@ def events_main(a) -> None:
         parity["ok"] = parity["ok"] and out["end_to_end"]["parity"]
         out["parity"] = parity["ok"]
     if not a.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(N, wl["seed"], a.cpu_seconds)
+        out["cpu_baseline"] = cpu_baseline(N, WORKLOADS[N]["seed"], a.cpu_seconds)
         out["cpu_baseline"]["config0"] = cpu_config0()
-    print(json.dumps(out), flush=True)
-    if parity["ok"] is False:
-        sys.exit(1)
 
 
 def events_end_to_end(rec: dict, T: int) -> dict:
@@ -780,16 +878,24 @@ def run_main(a) -> None:
                 t0 = time.perf_counter()
                 res = one(0)
                 times.append(time.perf_counter() - t0)
-            btimes = []  # main.go's capacity-1000 events channel (main.go:53)
-            for _ in range(a.steps):
+            with open(os.path.join(root, "out", f"{N}x{N}x{T}.pgm"), "rb") as f:
+                pgm = f.read()  # the last timed Run's
+            btimes = []  # --full: main.go's capacity-1000 events channel (main.go:53)
+            for _ in range(a.steps if a.full else 0):
                 t0 = time.perf_counter()
                 bres = one(1000)
                 btimes.append(time.perf_counter() - t0)
         counts, last, final_alive = res
-        if bres != res:
+        if btimes and bres != res:
             raise RuntimeError(f"buffered run differs: {bres} vs {res}")
         with open(os.path.join(root, "out", f"{N}x{N}x{T}.pgm"), "rb") as f:
-            sha = hashlib.sha256(f.read()).hexdigest()
+            sha = hashlib.sha256(f.read()).hexdigest()  # the newest Run's
+    if a.dump_outputs:
+        from oracle.oracle import parse_pgm
+        dump_arrays(a.dump_outputs, {
+            "board": (parse_pgm(pgm, N, N) != 0).astype(np.float32),  # out/512x512x<T>.pgm as 0/1 cells
+            "event_counts": np.array([counts[k] for k in golhip.EVENT_NAMES], dtype=np.float64),
+            "final": np.array([final_alive, last], dtype=np.float64)})  # len(FinalTurnComplete.Alive), last turn
     dt = sum(times)
     if T == 100:  # the reference's own golden board
         fixture = "check/images/512x512x100.pgm (manifest sha256), check/alive/512x512.csv"
@@ -814,10 +920,11 @@ def run_main(a) -> None:
         "runs_per_s": round(a.steps / dt, 2),
         "ms_per_run_min": round(min(times) * 1e3, 3),
         "events_channel": "unbuffered (gol_test.go:15-47's make(chan gol.Event)): every send waits for the receive",
-        "buffered_1000": {"gcups": round(N * N * T * a.steps / sum(btimes) / 1e9, 4),
-                          "ms_per_run": round(sum(btimes) / a.steps * 1e3, 3),
-                          "note": "main.go:53's make(chan gol.Event, 1000), same events, same parity"},
     }
+    if btimes:
+        out["buffered_1000"] = {"gcups": round(N * N * T * a.steps / sum(btimes) / 1e9, 4),
+                                "ms_per_run": round(sum(btimes) / a.steps * 1e3, 3),
+                                "note": "main.go:53's make(chan gol.Event, 1000), same events, same parity"}
     if not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_config0()
     print(json.dumps(out), flush=True)
@@ -953,14 +1060,16 @@ class RankEnv:
             self.dist.destroy_process_group()
 
 
-def measure(a, env, workload: int, steps: int, warmup: int, warmup_seconds: float, tps: int | None = None) -> dict:
+def measure(a, env, workload: int, steps: int, warmup: int, warmup_seconds: float, tps: int | None = None,
+            dump: str | None = None) -> dict:
     """One strong-scaled board of `workload` over the job's ranks: rank r
     owns rows [r H / N, (r + 1) H / N) and steps them with its RCCL halo ring.
     Parity: the first untimed step starts from the freshly filled board, so
     its digest and alive count (summed over ranks) must equal the config's
     tests/golden/fullsize.json checkpoint at `tps` turns.  Then untimed
     warmup steps, then exactly `steps` timed steps between a barrier +
-    synchronize on both sides, the time the max over ranks."""
+    synchronize on both sides, the time the max over ranks.  `dump`: the
+    directory the last step's board is written to (dump_board)."""
     wl = WORKLOADS[workload]
     world, rank = env.world, env.rank
     N = workload
@@ -989,9 +1098,25 @@ def measure(a, env, workload: int, steps: int, warmup: int, warmup_seconds: floa
                 raise SystemExit(f"RCCL ring reports rank {comm['rank']} of {comm['nranks']}, "
                                  f"expected {rank} of {world}")
         board.fill_random(wl["seed"])
+        # the clock-bound warmup first, then the board is filled again: the W
+        # warmup steps and the timed steps always run turns 1 .. (W + steps) x
+        # tps of the seed's board, so the last step's board is the same from
+        # run to run (--dump-outputs).  Every rank runs the same number of
+        # extra steps (decided by rank 0's clock)
+        extra = 0
+        if warmup_seconds > 0:
+            env.stage(tag + "warmup steps (--warmup-seconds)")
+            t_w = time.perf_counter()
+            board.step(tps)
+            board.sync()
+            per = max(1e-6, time.perf_counter() - t_w)
+            extra = 1 + env.bcast(min(1000, int(max(0.0, warmup_seconds - per) / per)))
+            for _ in range(extra - 1):
+                board.step(tps)
+            board.sync()
+            board.fill_random(wl["seed"])
         # warmup step 1 from the fresh board = the parity run
         env.stage(tag + "parity step (first warmup step, halo exchanges)")
-        t_w = time.perf_counter()
         board.step(tps)
         board.sync()
         digest = env.gsum(board.board_hash())
@@ -1006,17 +1131,8 @@ def measure(a, env, workload: int, steps: int, warmup: int, warmup_seconds: floa
             cp = None
         parity["ok"] = None if cp is None else (cp["hash"] == parity["digest"] and cp["alive"] == alive)
         parity["fixture"] = "tests/golden/fullsize.json " + (f"{wl['key']} turn {tps}" if cp else "(no checkpoint)")
-        for _ in range(max(0, warmup - 1)):
-            board.step(tps)
-        board.sync()
-        # every rank runs the same number of extra warmup steps (decided by rank 0's clock)
-        extra = 0
-        done_w = max(1, warmup)
-        if warmup_seconds > 0:
-            per = max(1e-6, (time.perf_counter() - t_w) / done_w)
-            extra = env.bcast(min(1000, int(max(0.0, warmup_seconds - (time.perf_counter() - t_w)) / per)))
         env.stage(tag + "warmup steps")
-        for _ in range(extra):
+        for _ in range(max(0, warmup - 1)):
             board.step(tps)
         env.barrier(board)
         env.stage(tag + "timed steps")
@@ -1033,6 +1149,9 @@ def measure(a, env, workload: int, steps: int, warmup: int, warmup_seconds: floa
             env.dist.barrier()
         perf = board.perf()
         alive_end, at_turn = board.alive_count(global_sum=ringed)
+        if dump:
+            dump_board(dump, board, W, H, row0, rows, env.gsum(board.board_hash()), alive_end, at_turn,
+                       f".rank{rank}" if world > 1 else "", rank == 0)
         me = {"rank": rank, "row0": row0, "rows": rows, "comm": comm, "seconds": round(dt_rank, 6),
               "region_ms": round(region_ms, 3), "launches": perf["step_launches"] + perf["persist_launches"],
               "words_per_lane": perf["words_per_lane"], "halo_exchanges": perf.get("halo_exchanges", 0),
@@ -1080,7 +1199,7 @@ def main(env_factory=RankEnv):
         error_line(a, f"--gpus {a.gpus} but WORLD_SIZE={world}")
         sys.exit(2)
     env = env_factory(a, world, rank, local)
-    m = measure(a, env, a.workload, a.steps, a.warmup, a.warmup_seconds, a.turns_per_step)
+    m = measure(a, env, a.workload, a.steps, a.warmup, a.warmup_seconds, a.turns_per_step, a.dump_outputs)
     out = {"metric": METRIC, **{k: m[k] for k in ("value", "unit", "n_gpus", "steps", "warmup",
                                                     "warmup_extra_steps", "ms_per_step")},
            "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
@@ -1092,7 +1211,7 @@ def main(env_factory=RankEnv):
     out["final_alive"], out["final_turn"] = m["final_alive"], m["final_turn"]
     if a.workload == 65536 and a.configs3:
         # north_star's strong-scaling target is configs[3] (262144^2, >= 80 % at 8
-        # GPUs): every default line also measures it over the same ranks, so the
+        # GPUs): every default --full line also measures it over the same ranks, so the
         # driver's one-shot N = 1/2/4/8 runs record both curves.  `value` stays
         # configs[2]'s (BENCH and SCALE lines stay comparable across rounds).
         c3 = measure(a, env, 262144, a.steps, 1, a.configs3_warmup_seconds)

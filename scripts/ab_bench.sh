@@ -4,7 +4,7 @@ out=$1; args=$2; shift 2
 mkdir -p $out
 for round in 1 2; do
   for lib in "$@"; do
-    GOLHIP_LIB=$lib timeout -k 10 200 python -u bench.py --no-cpu-baseline $args > $out/tmp.json 2> $out/tmp.err || { tail $out/tmp.err; exit 1; }
+    GOLHIP_LIB=$lib timeout -k 10 200 python -u bench.py --full --no-cpu-baseline $args > $out/tmp.json 2> $out/tmp.err || { tail $out/tmp.err; exit 1; }
     python3 -c "
 import json
 d=json.load(open('$out/tmp.json')); r=d['roofline']

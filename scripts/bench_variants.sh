@@ -3,7 +3,7 @@
 out=$1; shift
 mkdir -p $(dirname $out)
 for args in "$@"; do
-  timeout -k 10 200 python -u bench.py --no-cpu-baseline $args > $out.tmp.json 2> $out.tmp.err || { tail $out.tmp.err; exit 1; }
+  timeout -k 10 200 python -u bench.py --full --no-cpu-baseline $args > $out.tmp.json 2> $out.tmp.err || { tail $out.tmp.err; exit 1; }
   python3 - "$args" "$out.tmp.json" <<'PY' | tee -a $out
 import json, sys
 d = json.load(open(sys.argv[2])); r = d["roofline"]

@@ -10,6 +10,7 @@ import subprocess
 import sys
 import textwrap
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -124,6 +125,11 @@ class _FakeBoard:
     def perf_reset(self): pass
     def close(self): self.closed = True
 
+    def snapshot_rows(self, row, nrows):  # row r holds r in its first word
+        out = np.zeros((nrows, self.W // 32), dtype=np.uint32)
+        out[:, 0] = np.arange(row, row + nrows)
+        return out
+
     def _cp(self):
         return FULLSIZE[self.key]["checkpoints"].get(str(self.turn))
 
@@ -196,8 +202,9 @@ def test_default_line_carries_a_configs3_block(monkeypatch, capsys, world):
     if world > 1:
         monkeypatch.setenv("WORLD_SIZE", str(world))
         monkeypatch.setenv("RANK", "0")
-    code, (line,) = _run_main(monkeypatch, capsys, ["--gpus", str(world), "--steps", "3", "--no-cpu-baseline",
-                                                    "--warmup-seconds", "0", "--configs3-warmup-seconds", "0"], env)
+    code, (line,) = _run_main(monkeypatch, capsys, ["--gpus", str(world), "--steps", "3", "--full",
+                                                    "--no-cpu-baseline", "--warmup-seconds", "0",
+                                                    "--configs3-warmup-seconds", "0"], env)
     assert code == 0 and line["parity"] is True
     assert line["config"]["board"] == [65536, 65536] and line["value"] > 0  # the primary value stays configs[2]
     c3 = line["configs3"]
@@ -215,8 +222,8 @@ def test_default_line_carries_a_configs3_block(monkeypatch, capsys, world):
 
 def test_configs3_parity_failure_fails_the_line(monkeypatch, capsys):
     env, _ = _fake_env(1, bad=("c3",))
-    code, (line,) = _run_main(monkeypatch, capsys, ["--steps", "1", "--no-cpu-baseline", "--warmup-seconds", "0",
-                                                    "--configs3-warmup-seconds", "0"], env)
+    code, (line,) = _run_main(monkeypatch, capsys, ["--steps", "1", "--full", "--no-cpu-baseline", "--warmup-seconds",
+                                                    "0", "--configs3-warmup-seconds", "0"], env)
     assert code == 1 and line["parity"] is False and line["configs3"]["parity"] is False
     assert line["parity_check"]["ok"] is True  # configs[2] itself was right
 
@@ -226,6 +233,56 @@ def test_no_configs3_flag_and_other_workloads_skip_the_block(monkeypatch, capsys
     code, (line,) = _run_main(monkeypatch, capsys, ["--steps", "1", "--no-cpu-baseline", "--warmup-seconds", "0",
                                                     "--no-configs3"], env)
     assert code == 0 and "configs3" not in line and [b.W for b in boards] == [65536]
+
+
+def test_plain_run_measures_the_headline_only(monkeypatch, capsys):
+    """Without --full: one board (configs[2]), no configs3 block, no CPU
+    baseline, exactly --steps timed steps after --warmup untimed ones."""
+    env, boards = _fake_env(1)
+    monkeypatch.setattr(bench, "cpu_baseline", lambda *a, **k: pytest.fail("cpu_baseline in a plain run"))
+    code, (line,) = _run_main(monkeypatch, capsys, ["--gpus", "1", "--steps", "4", "--warmup", "2",
+                                                    "--warmup-seconds", "0"], env)
+    assert code == 0 and line["parity"] is True
+    assert "configs3" not in line and "cpu_baseline" not in line and [b.W for b in boards] == [65536]
+    assert line["steps"] == 4 and line["final_turn"] == (2 + 4) * 1000 and line["ms_per_step"] >= 0
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(line)
+
+
+def test_clock_bound_warmup_leaves_the_timed_turns_alone(monkeypatch, capsys):
+    """--warmup-seconds runs before the board is filled again: the parity step
+    is turn 1000 of the fresh board and the last timed step ends at turn
+    (W + K) x 1000 however many extra steps the clock asked for."""
+    env, boards = _fake_env(1)
+    code, (line,) = _run_main(monkeypatch, capsys, ["--steps", "2", "--warmup", "1", "--warmup-seconds", "0.05"], env)
+    assert code == 0 and line["parity"] is True and line["warmup_extra_steps"] >= 1
+    assert line["final_turn"] == 3000
+
+
+def test_dump_outputs_writes_the_last_steps_board(monkeypatch, capsys, tmp_path):
+    env, boards = _fake_env(1)
+    argv = ["--steps", "2", "--warmup-seconds", "0", "--dump-outputs"]
+    runs = []
+    for d in ("a", "b"):
+        code, (line,) = _run_main(monkeypatch, capsys, argv + [str(tmp_path / d)], env)
+        assert code == 0
+        runs.append({f.name: np.load(f) for f in sorted((tmp_path / d).iterdir())})
+    a, b = runs
+    assert sorted(a) == ["board_alive.npy", "board_digest.npy", "board_row_index.npy", "board_rows.npy"]
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    rows = a["board_row_index.npy"].astype(np.int64)
+    assert rows[0] == 0 and rows[-1] == 65535 and len(set(rows)) == len(rows) > 100
+    # the fake board's row r holds r in its first word: cell c of row r is bit c of r
+    assert a["board_rows.npy"].shape == (len(rows), 65536)
+    assert np.array_equal(a["board_rows.npy"][:, :32], (rows[:, None] >> np.arange(32)) & 1)
+    assert not a["board_rows.npy"][:, 32:].any()
+    assert list(a["board_alive.npy"]) == [0, 3000]  # no checkpoint at turn 3000: the fake counts 0
+    assert list(a["board_digest.npy"]) == [0, 0]
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    bench.dump_board(str(tmp_path / "c"), boards[-1], 65536, 65536, 0, 65536, 0x123456789ABCDEF0, 7, 9)
+    assert list(np.load(tmp_path / "c" / "board_digest.npy")) == [0x12345678, 0x9ABCDEF0]
+    assert list(np.load(tmp_path / "c" / "board_alive.npy")) == [7, 9]
 
 
 def test_cpu_share_is_measured():

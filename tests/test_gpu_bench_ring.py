@@ -76,8 +76,8 @@ def _free_port() -> int:
 @pytest.mark.timeout(450)
 def test_bench_two_ranks_host_ring(tmp_path):
     world = 2
-    argv = ["--gpus", str(world), "--steps", "1", "--warmup", "1", "--warmup-seconds", "0",
-            "--configs3-warmup-seconds", "0", "--stage-timeout", "200"]
+    argv = ["--gpus", str(world), "--steps", "1", "--warmup", "1", "--warmup-seconds", "0", "--full",
+            "--no-cpu-baseline", "--configs3-warmup-seconds", "0", "--stage-timeout", "200"]
     script = tmp_path / "rank_main.py"
     script.write_text(RANK_MAIN.format(root=ROOT, argv=argv))
     port = _free_port()
