@@ -110,6 +110,32 @@ struct FlipBuffer {
     }
 };
 
+// Page-locked frames of the live view, written by the view kernel itself: two
+// halves of `per_half` frames, so the frame a consumer may be copying (the
+// last one published, in the half of the previous batch) is never the one the
+// device writes.  At most kViewRingBytes in all.
+constexpr uint64_t kViewRingBytes = 64ull << 20;
+struct ViewRing {
+    uint8_t *p = nullptr;
+    uint64_t frame_bytes = 0;
+    int64_t per_half = 0;
+    int half = 0;  // the half the next batch writes
+    ViewRing(const golhip_view_t &v, int64_t batch_frames) {
+        frame_bytes = (uint64_t)v.out_w * (uint64_t)v.out_h * (v.format == GOLHIP_VIEW_GRAY8 ? 1u : 4u);
+        if (frame_bytes == 0 || 2 * frame_bytes > kViewRingBytes)
+            throw std::runtime_error("live view: a frame of " + std::to_string(frame_bytes) +
+                                     " bytes does not fit the 64 MiB frame ring twice");
+        per_half = std::max<int64_t>(1, std::min<int64_t>(batch_frames, (int64_t)(kViewRingBytes / 2 / frame_bytes)));
+        void *q = nullptr;
+        check(golhip_host_alloc(2 * (uint64_t)per_half * frame_bytes, &q));
+        p = static_cast<uint8_t *>(q);
+    }
+    uint8_t *slot(int h, int64_t i) const { return p + ((uint64_t)h * per_half + (uint64_t)i) * frame_bytes; }
+    ~ViewRing() {
+        if (p) golhip_host_free(p);
+    }
+};
+
 struct Engine {
     std::vector<golhip_t> hs;
     std::vector<int64_t> row0;
@@ -119,6 +145,9 @@ struct Engine {
         const int strips = opt.strips >= 0 ? opt.strips : env_int("GOL_STRIPS", 0);
         int n = strips > 0 ? strips : std::max(1, ngpu);
         n = (int)std::min<int64_t>(n, hgt);
+        if (n > 1 && opt.view.scale > 0)
+            throw std::runtime_error("live view: a run of " + std::to_string(n) +
+                                     " strips (GOL_STRIPS / GOL_NGPU) has no view; run it on one strip");
         if (n <= 1) {
             hs.push_back(nullptr);
             row0.push_back(0);
@@ -236,6 +265,31 @@ void Run(Params p, Chan<Event> *events, Chan<char32_t> *keyPresses, const RunOpt
 
     Engine board(W, H, opt);
     board.load(raster.data());
+
+    // Live view: frames land in the ring and are published by pointer.  With
+    // cell events the turns keep the flip stream, in batches that end on the
+    // frame turns, and golhip_view_frame renders between them; without, the
+    // batch itself is golhip_view_stream.
+    const bool view_on = opt.view.scale > 0;
+    if (view_on && (!opt.view_sink || opt.view_every < 1)) throw std::runtime_error("live view: no sink, or every < 1");
+    const int64_t batch_turns = opt.batch_turns > 0 ? opt.batch_turns : (opt.cell_events ? 64 : 256);
+    std::unique_ptr<ViewRing> ring;
+    if (view_on) ring.reset(new ViewRing(opt.view, opt.cell_events ? 1 : std::max<int64_t>(1, batch_turns / opt.view_every)));
+    // the current board's frame into the ring's next half, published at once
+    auto view_now = [&] {
+        int64_t at = 0;
+        uint8_t *f = ring->slot(ring->half, 0);
+        check(golhip_view_frame(board.hs[0], &opt.view, f, ring->frame_bytes, &at));
+        opt.view_sink->publish(f, ring->frame_bytes, at);
+        ring->half ^= 1;
+    };
+    struct KeepLastFrame {  // the sink outlives the ring
+        ViewSink *s;
+        ~KeepLastFrame() {
+            if (s) s->keep_copy();
+        }
+    } keep_last{view_on ? opt.view_sink : nullptr};
+    if (view_on) view_now();  // turn 0, before the first event
 
     auto send = [&](Event e) {
         if (events) events->send(std::move(e));
@@ -394,7 +448,11 @@ void Run(Params p, Chan<Event> *events, Chan<char32_t> *keyPresses, const RunOpt
         // otherwise fused step launches.  `mu` is held only for the call, so
         // the ticker, s/q snapshots and p (which takes `mu`, as the
         // reference's pause does) act between batches, at a turn boundary.
-        const int64_t batch = opt.batch_turns > 0 ? opt.batch_turns : (opt.cell_events ? 64 : 256);
+        // with a view stream a batch ends on a frame and fills at most half the ring
+        const bool view_stream = view_on && !opt.cell_events;
+        const int64_t batch = !view_stream ? batch_turns
+                                           : std::max<int64_t>(1, std::min(batch_turns / opt.view_every, ring->per_half)) *
+                                                 opt.view_every;
         FlipBuffer fb;
         if (opt.cell_events) fb.grow((uint64_t)std::min<int64_t>(W * H * std::min<int64_t>(batch, 4), 64ll << 20));
         std::vector<uint64_t> counts((size_t)batch);
@@ -402,12 +460,21 @@ void Run(Params p, Chan<Event> *events, Chan<char32_t> *keyPresses, const RunOpt
         std::vector<Event> flip_evs;
         int64_t t = 0;
         while (t < p.Turns && !quit.load()) {
-            const int64_t want = std::min<int64_t>(batch, p.Turns - t);
+            int64_t want = std::min<int64_t>(batch, p.Turns - t);
+            if (view_on && !view_stream) want = std::min(want, opt.view_every - t % opt.view_every);  // end on a frame turn
             int64_t done = want;
             uint64_t n = 0;
+            int view_half = 0;
             {
                 std::lock_guard<std::mutex> g(mu);
-                if (opt.cell_events) {
+                if (view_stream) {
+                    // frame i of the batch shows turn t + (i + 1) * every
+                    uint64_t nf = 0;
+                    view_half = ring->half;
+                    check(golhip_view_stream(board.hs[0], want, opt.view_every, &opt.view, ring->slot(view_half, 0),
+                                             (uint64_t)ring->per_half, &nf, &done));
+                    ring->half ^= 1;
+                } else if (opt.cell_events) {
                     int rc = board.flip_stream(want, fb, counts.data(), &done, &n);
                     if (rc == GOLHIP_ERANGE) {  // one turn needs more than the buffer: grow, nothing advanced
                         fb.grow(n);
@@ -419,6 +486,7 @@ void Run(Params p, Chan<Event> *events, Chan<char32_t> *keyPresses, const RunOpt
                 }
                 t += done;
                 turn = t;
+                if (view_on && !view_stream && t % opt.view_every == 0) view_now();  // ahead of the batch's events
             }
             // let a queued ticker / key handler take `mu` before the next batch
             while (waiters.load() > 0) std::this_thread::sleep_for(std::chrono::microseconds(20));
@@ -445,6 +513,9 @@ void Run(Params p, Chan<Event> *events, Chan<char32_t> *keyPresses, const RunOpt
                     }
                     off += n;
                 }
+                if (view_stream && (i + 1) % opt.view_every == 0)  // (t0 is a multiple of every)
+                    opt.view_sink->publish(ring->slot(view_half, (i + 1) / opt.view_every - 1), ring->frame_bytes,
+                                           completed);
                 if (opt.turn_events) {
                     Event ev;
                     ev.kind = EventKind::TurnComplete;
@@ -454,6 +525,7 @@ void Run(Params p, Chan<Event> *events, Chan<char32_t> *keyPresses, const RunOpt
             }
         }
         stop_helpers();
+        if (view_on && opt.view_sink->turn() != turn.load()) view_now();  // turns after the last frame
         if (quit.load()) {
             // `q` (:244-261): snapshot already written; the reference os.Exit(0)s
             // without FinalTurnComplete.  The mirror ends the run instead.
@@ -505,6 +577,8 @@ struct golrun {
     std::string err;
     std::atomic<bool> done{false};
     gol::Event current;
+    bool has_view = false;
+    gol::ViewSink view;
     golrun(size_t cap, bool k) : events(cap), keys(16), use_keys(k) {}
 };
 
@@ -522,7 +596,27 @@ const char *golrun_last_error(void) { return g_run_err.c_str(); }
 
 int golrun_start(int64_t turns, int64_t threads, int64_t width, int64_t height, const char *root, int32_t device,
                  uint32_t flags, int32_t events_cap, int32_t ticker_ms, golrun_t *out) {
+    return golrun_start_view(turns, threads, width, height, root, device, flags, events_cap, ticker_ms, nullptr, 1, out);
+}
+
+int golrun_view_frame(golrun_t r, void *out, uint64_t cap_bytes, int64_t *turn) {
+    if (!r || !out) return run_fail("bad arguments");
+    if (!r->has_view) return run_fail("the run has no view (golrun_start_view)");
+    uint64_t bytes = 0;
+    switch (r->view.fetch(out, cap_bytes, turn, &bytes)) {
+    case 0: return GOLHIP_OK;
+    case 1: return run_fail("no frame published yet");
+    default:
+        g_run_err = "buffer holds " + std::to_string(cap_bytes) + " bytes, the frame needs " + std::to_string(bytes);
+        return GOLHIP_ERANGE;
+    }
+}
+
+int golrun_start_view(int64_t turns, int64_t threads, int64_t width, int64_t height, const char *root,
+                      int32_t device, uint32_t flags, int32_t events_cap, int32_t ticker_ms,
+                      const golhip_view_t *view, int32_t every, golrun_t *out) {
     if (!out || !root || events_cap < 0) return run_fail("bad arguments");
+    if (view && (view->scale < 1 || every < 1)) return run_fail("view scale and every must be >= 1");
     gol::Params p;
     p.Turns = turns;
     p.Threads = threads;
@@ -536,6 +630,12 @@ int golrun_start(int64_t turns, int64_t threads, int64_t width, int64_t height, 
     o.turn_events = (flags & GOLRUN_FLAG_NO_TURN_EVENTS) == 0;
     if (ticker_ms > 0) o.ticker_seconds = ticker_ms / 1000.0;
     golrun *r = new golrun((size_t)events_cap, (flags & GOLRUN_FLAG_KEYS) != 0);
+    if (view) {
+        r->has_view = true;
+        o.view = *view;
+        o.view_every = every;
+        o.view_sink = &r->view;
+    }
     r->th = std::thread([r, p, o] {
         try {
             gol::Run(p, &r->events, r->use_keys ? &r->keys : nullptr, o);

@@ -19,11 +19,14 @@
 #include <condition_variable>
 #include <cstdint>
 #include <deque>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <stdexcept>
 #include <string>
 #include <vector>
+
+#include "../../include/golhip.h"
 
 // Go's int is 64-bit (gol.go:4-9, event.go:19-68, util/cell.go:4-6): every
 // integer of the mirror's API is int64_t, so a 262144^2 board's ~6.5e9 alive
@@ -324,6 +327,55 @@ class Chan {
     std::atomic<int> recv_waiting_{0};     // receivers inside recv0 (they own the next offer)
 };
 
+// The live view's newest frame (RunOptions::view_sink): the run publishes a
+// frame by swapping a pointer under the mutex, a consumer (the window's
+// thread, golrun_view_frame) copies it out under the same mutex.  A published
+// frame stays valid until the next one is published.
+class ViewSink {
+   public:
+    void publish(const void *frame, uint64_t bytes, int64_t turn) {
+        {
+            std::lock_guard<std::mutex> g(mu_);
+            frame_ = frame, bytes_ = bytes, turn_ = turn;
+        }
+        if (on_publish) on_publish(frame, bytes, turn);
+    }
+    // Optional: called on the run's thread with every frame as it is published
+    // (set before the run starts), for a consumer that must not miss one.
+    std::function<void(const void *, uint64_t, int64_t)> on_publish;
+    // Copies the newest frame to out: 0 and *turn = the turn its pixels show;
+    // 1 = nothing published yet (or the run's frames are gone); 2 = cap is
+    // smaller than the frame (*bytes says how large it is).
+    int fetch(void *out, uint64_t cap, int64_t *turn, uint64_t *bytes = nullptr) {
+        std::lock_guard<std::mutex> g(mu_);
+        if (bytes) *bytes = bytes_;
+        if (!frame_) return 1;
+        if (cap < bytes_ || !out) return 2;
+        std::copy_n(static_cast<const uint8_t *>(frame_), bytes_, static_cast<uint8_t *>(out));
+        if (turn) *turn = turn_;
+        return 0;
+    }
+    int64_t turn() {
+        std::lock_guard<std::mutex> g(mu_);
+        return frame_ ? turn_ : -1;
+    }
+    // The run keeps the last frame here when it ends (its ring is freed).
+    void keep_copy() {
+        std::lock_guard<std::mutex> g(mu_);
+        if (!frame_) return;
+        const uint8_t *f = static_cast<const uint8_t *>(frame_);
+        last_.assign(f, f + bytes_);
+        frame_ = last_.data();
+    }
+
+   private:
+    std::mutex mu_;
+    const void *frame_ = nullptr;
+    uint64_t bytes_ = 0;
+    int64_t turn_ = -1;
+    std::vector<uint8_t> last_;
+};
+
 // Host-mirror options beyond the Go API (all default to the reference's
 // documented contract; see DESIGN.md "Quirks").
 struct RunOptions {
@@ -343,6 +395,15 @@ struct RunOptions {
     // on device 0).  -1: from the environment, GOL_NGPU / GOL_STRIPS (unset: 1).
     int ngpu = -1;
     int strips = -1;
+    // Live view (the reference's SDL window, sdl/window.go, as pixels): with
+    // view.scale > 0 the run renders the viewport on the device
+    // (golhip_view_stream / golhip_view_frame) after every view_every-th turn
+    // and publishes each frame to view_sink before that turn's TurnComplete;
+    // turn 0's frame before the first event, the final board's before
+    // FinalTurnComplete.  Off by default (scale 0).  One strip only.
+    golhip_view_t view{0, 0, 0, 0, 0, GOLHIP_VIEW_ARGB8888};
+    int64_t view_every = 1;
+    ViewSink *view_sink = nullptr;
 };
 
 // The PGM goroutine's file formats (io.go:42-126).

@@ -257,6 +257,22 @@ int flip_turn_blocks_per_cu(bool contig);
 // device-visible memory, e.g. page-locked host memory (the host-link probe)
 hipError_t launch_host_write_probe(void *dst, uint64_t bytes, int blocks, uint32_t tag, hipStream_t s);
 
+// gol_view.hip (K7): a frame of out_w x out_h pixels, one per s x s block of
+// cells from (x0, y0) on, wrapping in x and y (golhip_view_frame states the
+// pixel).  `rows`: the board's local row 0 in layout `il`; H: its rows (y
+// wraps there; y0 is a local row).  The caller guarantees 0 <= x0 < W,
+// 0 <= y0 < H, 1 <= s, out_w * s <= W, out_h * s <= H.
+struct ViewArgs {
+    const uint32_t *rows;
+    void *out;     // device-visible frame: out_w * out_h pixels of `format`
+    int W, Ww, H;
+    int x0, y0, s, out_w, out_h;
+    int il;        // 0 canonical, 2 pairs, 4 quads
+    int format;    // GOLHIP_VIEW_*
+    int ngr, gfirst, vec, pb;  // set by launch_view
+};
+hipError_t launch_view(ViewArgs a, hipStream_t s);
+
 // "NAME=value ..." of the build's tuning macros (golhip_build_info).
 const char *build_info();
 

@@ -230,12 +230,14 @@ struct golhip {
     std::vector<hipEvent_t> ev_pool;
     struct Timed {
         hipEvent_t e0, e1;
-        int kind;  // 0 per-launch step, 1 resident step, 2 flip turn (K5), 3 halo exchange
+        int kind;  // 0 per-launch step, 1 resident step, 2 flip turn (K5), 3 halo exchange, 4 view frame (K7)
     };
     std::vector<Timed> ev_pending;
     double step_ms = 0, persist_ms = 0;
     int64_t step_launches = 0, step_turns = 0, halo_bytes = 0;
     int64_t persist_turns = 0;
+    int64_t view_frames = 0;  // frames rendered (K7)
+    double view_ms = 0;
 
     std::mutex mu;
 
@@ -586,7 +588,9 @@ int drain_events(golhip_t h) {
         HIP_OR_FAIL(hipEventSynchronize(p.e1));
         float ms = 0;
         HIP_OR_FAIL(hipEventElapsedTime(&ms, p.e0, p.e1));
-        (p.kind == 1 ? h->persist_ms : p.kind == 2 ? h->flip_ms : p.kind == 3 ? h->halo_ms : h->step_ms) += ms;
+        double &sum = p.kind == 1 ? h->persist_ms : p.kind == 2 ? h->flip_ms : p.kind == 3 ? h->halo_ms
+                      : p.kind == 4 ? h->view_ms : h->step_ms;
+        sum += ms;
         h->ev_pool.push_back(p.e0);
         h->ev_pool.push_back(p.e1);
     }
@@ -2316,14 +2320,10 @@ int step_locked(golhip_t h, int64_t nturns, int32_t want_flips) {
     }
     return GOLHIP_OK;
 }
-}  // namespace
 
-extern "C" {
-
-int golhip_step(golhip_t h, int64_t nturns, int32_t want_flips) {
-    if (int rc = check(h)) return rc;
-    if (nturns < 0) return fail(GOLHIP_EINVAL, "nturns %lld", (long long)nturns);
-    std::lock_guard<std::mutex> g(h->mu);
+// golhip_step after its argument checks, with h->mu held: step_locked under
+// the resident-launch guard (also each batch of golhip_view_stream).
+int step_checked_locked(golhip_t h, int64_t nturns, int32_t want_flips) {
     if (!h->loaded) return fail(GOLHIP_EINVAL, "no board loaded");
     if (h->nranks == 1 && !h->torus()) return fail(GOLHIP_EINVAL, "strip handle needs golhip_comm_init or golhip_group_step");
     if (int rc = set_dev(h)) return rc;
@@ -2383,6 +2383,16 @@ int golhip_step(golhip_t h, int64_t nturns, int32_t want_flips) {
     h->alive_turn = -1;
     h->flips_valid = false;
     return step_locked(h, nturns, want_flips);
+}
+}  // namespace
+
+extern "C" {
+
+int golhip_step(golhip_t h, int64_t nturns, int32_t want_flips) {
+    if (int rc = check(h)) return rc;
+    if (nturns < 0) return fail(GOLHIP_EINVAL, "nturns %lld", (long long)nturns);
+    std::lock_guard<std::mutex> g(h->mu);
+    return step_checked_locked(h, nturns, want_flips);
 }
 
 }  // extern "C"
@@ -2692,6 +2702,128 @@ int golhip_board_hash(golhip_t h, uint64_t *hash) {
     return GOLHIP_OK;
 }
 
+}  // extern "C"
+
+namespace {
+// ---------------------------------------------------------------------------
+// live view (K7, gol_view.hip)
+// ---------------------------------------------------------------------------
+// Checks a view against the handle (h->mu held); *bytes = one frame.
+int view_check(golhip_t h, const golhip_view_t *v, uint64_t *bytes) {
+    if (!v) return fail(GOLHIP_EINVAL, "view is null");
+    if (v->format != GOLHIP_VIEW_ARGB8888 && v->format != GOLHIP_VIEW_GRAY8)
+        return fail(GOLHIP_EINVAL, "view format %d", v->format);
+    if (v->scale < 1 || v->scale > GOLHIP_VIEW_MAX_SCALE)
+        return fail(GOLHIP_EINVAL, "view scale %d not in [1, %d]", v->scale, GOLHIP_VIEW_MAX_SCALE);
+    if (v->out_w < 1 || v->out_h < 1) return fail(GOLHIP_EINVAL, "view frame %d x %d", v->out_w, v->out_h);
+    if (v->x0 < 0 || v->x0 >= h->W || v->y0 < 0 || v->y0 >= h->H)
+        return fail(GOLHIP_EINVAL, "view origin (%d, %d) outside the %d x %d board", v->x0, v->y0, h->W, h->H);
+    if ((int64_t)v->out_w * v->scale > h->W || (int64_t)v->out_h * v->scale > h->H)
+        return fail(GOLHIP_EINVAL, "view of %d x %d pixels at scale %d is more than one lap of the %d x %d board",
+                    v->out_w, v->out_h, v->scale, h->W, h->H);
+    if (h->rows != h->H &&
+        (v->y0 < h->row0 || (int64_t)v->y0 + (int64_t)v->out_h * v->scale > (int64_t)h->row0 + h->rows))
+        return fail(GOLHIP_EINVAL, "view rows [%d, %lld) leave the strip's rows [%d, %d)", v->y0,
+                    (long long)v->y0 + (long long)v->out_h * v->scale, h->row0, h->row0 + h->rows);
+    if (!h->loaded) return fail(GOLHIP_EINVAL, "no board loaded");
+    *bytes = (uint64_t)v->out_w * (uint64_t)v->out_h * (v->format == GOLHIP_VIEW_GRAY8 ? 1u : 4u);
+    return GOLHIP_OK;
+}
+
+// Enqueue one frame of the current board into device-visible memory `dst`.
+int view_launch(golhip_t h, const golhip_view_t *v, void *dst) {
+    golk::ViewArgs a{};
+    a.rows = h->cur_rows();
+    a.out = dst;
+    a.W = h->W;
+    a.Ww = h->Ww;
+    a.H = h->rows;
+    a.x0 = v->x0;
+    a.y0 = v->y0 - h->row0;
+    a.s = v->scale;
+    a.out_w = v->out_w;
+    a.out_h = v->out_h;
+    a.il = h->il;
+    a.format = v->format;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (h->flags & GOLHIP_FLAG_TIMING) {
+        e0 = take_event(h);
+        e1 = take_event(h);
+        if (!e0 || !e1) return fail(GOLHIP_EHIP, "hipEventCreate failed");
+        HIP_OR_FAIL(hipEventRecord(e0, h->stream));
+    }
+    const hipError_t e = golk::launch_view(a, h->stream);
+    if (e != hipSuccess) return fail(GOLHIP_EHIP, "view launch: %s", hipGetErrorString(e));
+    if (e1) {
+        HIP_OR_FAIL(hipEventRecord(e1, h->stream));
+        h->ev_pending.push_back({e0, e1, 4});
+        if (h->ev_pending.size() >= 4096)
+            if (int rc = drain_events(h)) return rc;
+    }
+    h->view_frames++;
+    return GOLHIP_OK;
+}
+
+// One frame to `out` (host): written there by the kernel if it is
+// golhip_host_alloc memory (`mapped`: its device address), else staged.
+int view_to_host(golhip_t h, const golhip_view_t *v, void *out, void *mapped, uint64_t bytes) {
+    if (mapped) return view_launch(h, v, mapped);
+    if (int rc = ensure_stage(h, (int64_t)bytes)) return rc;
+    if (int rc = view_launch(h, v, h->d_stage)) return rc;
+    HIP_OR_FAIL(hipMemcpyAsync(out, h->d_stage, (size_t)bytes, hipMemcpyDeviceToHost, h->stream));
+    return GOLHIP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int golhip_view_frame(golhip_t h, const golhip_view_t *v, void *out, uint64_t cap_bytes, int64_t *at_turn) {
+    if (int rc = check(h)) return rc;
+    if (!out) return fail(GOLHIP_EINVAL, "out is null");
+    std::lock_guard<std::mutex> g(h->mu);
+    uint64_t bytes = 0;
+    if (int rc = view_check(h, v, &bytes)) return rc;
+    if (cap_bytes < bytes)
+        return fail(GOLHIP_ERANGE, "buffer holds %llu bytes, the frame needs %llu", (unsigned long long)cap_bytes,
+                    (unsigned long long)bytes);
+    if (int rc = set_dev(h)) return rc;
+    if (int rc = view_to_host(h, v, out, mapped_device_ptr(out, (size_t)bytes), bytes)) return rc;
+    if (int rc = sync_stream(h)) return rc;
+    if (at_turn) *at_turn = h->turns;
+    return GOLHIP_OK;
+}
+
+int golhip_view_stream(golhip_t h, int64_t nturns, int64_t every, const golhip_view_t *v, void *out,
+                       uint64_t cap_frames, uint64_t *frames, int64_t *turns_done) {
+    if (int rc = check(h)) return rc;
+    if (frames) *frames = 0;
+    if (turns_done) *turns_done = 0;
+    if (nturns < 0) return fail(GOLHIP_EINVAL, "nturns %lld", (long long)nturns);
+    if (every < 1) return fail(GOLHIP_EINVAL, "every %lld", (long long)every);
+    std::lock_guard<std::mutex> g(h->mu);
+    uint64_t bytes = 0;
+    if (int rc = view_check(h, v, &bytes)) return rc;
+    if (h->nranks == 1 && !h->torus()) return fail(GOLHIP_EINVAL, "strip handle needs golhip_comm_init or golhip_group_step");
+    const uint64_t nf = (uint64_t)(nturns / every);
+    if (nf > cap_frames)
+        return fail(GOLHIP_ERANGE, "buffer holds %llu frames, %lld turns at every %lld need %llu",
+                    (unsigned long long)cap_frames, (long long)nturns, (long long)every, (unsigned long long)nf);
+    if (nf > 0 && !out) return fail(GOLHIP_EINVAL, "out is null");
+    if (int rc = set_dev(h)) return rc;
+    char *mapped = nf ? (char *)mapped_device_ptr(out, (size_t)(nf * bytes)) : nullptr;
+    const int64_t turns0 = h->turns;
+    for (uint64_t f = 0; f < nf; ++f) {
+        if (int rc = step_checked_locked(h, every, 0)) return rc;
+        if (int rc = view_to_host(h, v, (char *)out + f * bytes, mapped ? mapped + f * bytes : nullptr, bytes)) return rc;
+    }
+    if (int rc = step_checked_locked(h, nturns - (int64_t)nf * every, 0)) return rc;
+    if (nf > 0)
+        if (int rc = sync_stream(h)) return rc;
+    if (frames) *frames = nf;
+    if (turns_done) *turns_done = h->turns - turns0;
+    return GOLHIP_OK;
+}
+
 int golhip_perf(golhip_t h, golhip_perf_t *out) {
     if (int rc = check(h)) return rc;
     if (!out) return fail(GOLHIP_EINVAL, "null out");
@@ -2729,6 +2861,8 @@ int golhip_perf(golhip_t h, golhip_perf_t *out) {
     out->pair_launches = h->pair_launches;
     out->pair_turns = h->pair_turns;
     out->flip_resident_launches = h->flip_resident;
+    out->view_frames = h->view_frames;
+    out->view_kernel_ms = h->view_ms;
     out->words_per_lane = h->W % 32 == 0 ? wpl_for(h) : 0;
     out->persist_depth = h->W % 32 == 0 ? persist_depth_for(h, wpl_for(h)) : 0;
     return GOLHIP_OK;
@@ -2775,6 +2909,8 @@ int golhip_perf_reset(golhip_t h) {
     h->pair_launches = 0;
     h->pair_turns = 0;
     h->flip_resident = 0;
+    h->view_frames = 0;
+    h->view_ms = 0;
     return GOLHIP_OK;
 }
 

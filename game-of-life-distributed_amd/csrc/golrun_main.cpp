@@ -2,6 +2,7 @@
 // of gol.Run (gol_host.h) and libgolhip.so.
 //
 //   golrun [-t threads] [-w width] [-h height] [-turns n] [-noVis] [-root dir] [-device n]
+//          [-viewScale n] [-viewEvery n] [-viewDir dir]
 //
 // Same flags, defaults and output as main.go: "Threads: / Width: / Height:"
 // lines, then gol.Run on images/<w>x<h>.pgm with an events channel of
@@ -9,8 +10,15 @@
 // window in this build (sdl/ is out of scope): without -noVis
 // the run is headless too, and single-character lines on stdin (s, q, p, k)
 // are forwarded as key presses, the keys the SDL loop forwards (sdl/loop.go).
+// -viewScale n (0 = off, the default) renders the whole board on the device,
+// one GRAY8 pixel per n x n cells (width / n x height / n pixels), after every
+// -viewEvery-th turn (default 1) and writes every frame as
+// <viewDir>/view_<W>x<H>x<turn>.pgm (P5; -viewDir defaults to <root>/out/view):
+// the pixels a window would show (gol_host.h RunOptions::view).
 // The headless drain loop ends at FinalTurnComplete (main.go:59-66) or when
 // the events channel closes.
+#include <sys/stat.h>
+
 #include <climits>
 #include <cstdio>
 #include <cstdlib>
@@ -25,7 +33,7 @@ namespace {
 
 [[noreturn]] void usage(const char *msg) {
     std::fprintf(stderr, "golrun: %s\nusage: golrun [-t threads] [-w width] [-h height] [-turns n] [-noVis] "
-                         "[-root dir] [-device n]\n", msg);
+                         "[-root dir] [-device n] [-viewScale n] [-viewEvery n] [-viewDir dir]\n", msg);
     std::exit(2);
 }
 
@@ -46,6 +54,8 @@ int main(int argc, char **argv) {
     long long turns = 10000000000LL;  // main.go:37-41
     bool no_vis = false;
     gol::RunOptions opt;
+    long long view_scale = 0, view_every = 1;
+    std::string view_dir;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         if (a.rfind("--", 0) == 0) a = a.substr(1);  // Go's flag package accepts -flag and --flag
@@ -74,6 +84,12 @@ int main(int argc, char **argv) {
             opt.root = value();
         } else if (key == "-device") {
             opt.device = (int)parse_int(value(), "device");
+        } else if (key == "-viewScale") {
+            view_scale = parse_int(value(), "viewScale");
+        } else if (key == "-viewEvery") {
+            view_every = parse_int(value(), "viewEvery");
+        } else if (key == "-viewDir") {
+            view_dir = value();
         } else {
             usage(("flag provided but not defined: " + key).c_str());
         }
@@ -84,6 +100,34 @@ int main(int argc, char **argv) {
                 (long long)params.ImageHeight);
     std::fflush(stdout);
     if (!no_vis) std::fprintf(stderr, "golrun: no SDL window in this build; running headless (keys s/q/p/k on stdin)\n");
+
+    // live view: every published frame of the whole board goes to a PGM file
+    gol::ViewSink sink;
+    std::string view_error;
+    if (view_scale != 0) {
+        if (view_scale < 1 || view_scale > GOLHIP_VIEW_MAX_SCALE || view_every < 1 ||
+            view_scale > params.ImageWidth || view_scale > params.ImageHeight)
+            usage("-viewScale must be in [1, 1024] and at most the board's sides, -viewEvery >= 1");
+        if (view_dir.empty()) view_dir = opt.root + "/out/view";
+        opt.view = golhip_view_t{0, 0, (int32_t)view_scale, (int32_t)(params.ImageWidth / view_scale),
+                                 (int32_t)(params.ImageHeight / view_scale), GOLHIP_VIEW_GRAY8};
+        opt.view_every = view_every;
+        opt.view_sink = &sink;
+        const std::string stem = view_dir + "/view_" + std::to_string(params.ImageWidth) + "x" +
+                                 std::to_string(params.ImageHeight) + "x";
+        const std::string out_dir = opt.root + "/out";
+        const gol::RunOptions &o = opt;
+        sink.on_publish = [stem, out_dir, view_dir, &o, &view_error](const void *frame, uint64_t, int64_t turn) {
+            try {
+                mkdir(out_dir.c_str(), 0777);
+                mkdir(view_dir.c_str(), 0777);
+                gol::WritePgm(stem + std::to_string(turn) + ".pgm", o.view.out_w, o.view.out_h,
+                              static_cast<const uint8_t *>(frame));
+            } catch (const std::exception &e) {
+                if (view_error.empty()) view_error = e.what();
+            }
+        };
+    }
 
     gol::Chan<char32_t> keys(10);
     gol::Chan<gol::Event> events(1000);
@@ -110,6 +154,7 @@ int main(int argc, char **argv) {
     while (events.recv(ev)) {  // let Run finish (StateChange Quitting, close)
     }
     engine.join();
+    if (error.empty()) error = view_error;
     if (!error.empty()) {
         std::fprintf(stderr, "golrun: %s\n", error.c_str());
         return 1;

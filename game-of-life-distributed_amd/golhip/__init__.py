@@ -23,6 +23,8 @@ FLAG_TIMING = 0x1
 UNIQUE_ID_BYTES = 128
 MAX_TB_DEPTH = 32
 HALO_ROWS = 128  # GOLHIP_HALO_ROWS
+VIEW_ARGB, VIEW_GRAY8 = 0, 1  # GOLHIP_VIEW_ARGB8888, GOLHIP_VIEW_GRAY8
+VIEW_MAX_SCALE = 1024
 
 
 class GolHipError(RuntimeError):
@@ -64,6 +66,8 @@ class Perf(ctypes.Structure):
         ("pair_launches", ctypes.c_int64),
         ("pair_turns", ctypes.c_int64),
         ("flip_resident_launches", ctypes.c_int64),
+        ("view_frames", ctypes.c_int64),
+        ("view_kernel_ms", ctypes.c_double),
     ]
 
     def as_dict(self) -> dict:
@@ -76,6 +80,14 @@ class HaloPlan(ctypes.Structure):
         ("send_up_row", ctypes.c_int32), ("recv_top_row", ctypes.c_int32),
         ("send_down_row", ctypes.c_int32), ("recv_bottom_row", ctypes.c_int32),
         ("rows", ctypes.c_int32), ("bytes", ctypes.c_int64),
+    ]
+
+
+class View(ctypes.Structure):
+    """golhip_view_t"""
+    _fields_ = [
+        ("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("scale", ctypes.c_int32),
+        ("out_w", ctypes.c_int32), ("out_h", ctypes.c_int32), ("format", ctypes.c_int32),
     ]
 
 
@@ -145,6 +157,8 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "golhip_snapshot_bits": ([H, ctypes.c_void_p], ctypes.c_int),
         "golhip_snapshot_rows": ([H, i32, i32, ctypes.c_void_p], ctypes.c_int),
         "golhip_board_hash": ([H, P(u64)], ctypes.c_int),
+        "golhip_view_frame": ([H, P(View), ctypes.c_void_p, u64, P(i64)], ctypes.c_int),
+        "golhip_view_stream": ([H, i64, i64, P(View), ctypes.c_void_p, u64, P(u64), P(i64)], ctypes.c_int),
         "golhip_perf": ([H, P(Perf)], ctypes.c_int),
         "golhip_perf_reset": ([H], ctypes.c_int),
         "golhip_persist_trace": ([H, P(u64)], ctypes.c_int),
@@ -423,6 +437,52 @@ class Board:
         _check(load().golhip_board_hash(self._h, ctypes.byref(h)))
         return h.value
 
+    # live view
+    def _view(self, x0, y0, scale, out_w, out_h, fmt) -> View:
+        """golhip_view_t; a missing out_w / out_h is the largest that fits."""
+        if out_w is None:
+            out_w = self.width // max(scale, 1)
+        if out_h is None:
+            out_h = self.rows // max(scale, 1)
+        return View(x0, y0, scale, out_w, out_h, fmt)
+
+    def view_frame(self, x0: int = 0, y0: int = 0, scale: int = 1, out_w: int | None = None,
+                   out_h: int | None = None, fmt: int = VIEW_ARGB, out: np.ndarray | None = None):
+        """golhip_view_frame: (frame, turn).  The frame is (out_h, out_w) uint32
+        (VIEW_ARGB) or uint8 (VIEW_GRAY8), one pixel per scale x scale cells
+        from (x0, y0) on; `out` may be a host_array the kernel writes itself."""
+        v = self._view(x0, y0, scale, out_w, out_h, fmt)
+        dt = np.dtype(np.uint8 if fmt == VIEW_GRAY8 else np.uint32)
+        n = max(v.out_w, 0) * max(v.out_h, 0)
+        if out is None:
+            out = np.empty(max(n, 1), dtype=dt)
+        if out.dtype != dt or out.size < n or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a C-contiguous {dt} array of >= {n} pixels")
+        t = ctypes.c_int64()
+        _check(load().golhip_view_frame(self._h, ctypes.byref(v), _ptr(out), out.size * dt.itemsize, ctypes.byref(t)))
+        return out.reshape(-1)[:n].reshape(v.out_h, v.out_w), t.value
+
+    def view_stream(self, nturns: int, every: int, x0: int = 0, y0: int = 0, scale: int = 1,
+                    out_w: int | None = None, out_h: int | None = None, fmt: int = VIEW_ARGB,
+                    out: np.ndarray | None = None, cap_frames: int | None = None):
+        """golhip_view_stream: advance nturns turns with a frame behind every
+        `every`-th; returns (frames, turns_done), frames (n, out_h, out_w).
+        Raises GolHipError (ERANGE, nothing advanced) when `out` (or
+        cap_frames) holds fewer than nturns // every frames."""
+        v = self._view(x0, y0, scale, out_w, out_h, fmt)
+        dt = np.dtype(np.uint8 if fmt == VIEW_GRAY8 else np.uint32)
+        n = max(v.out_w, 0) * max(v.out_h, 0)
+        if out is None:
+            cap = nturns // every if cap_frames is None and every > 0 else (cap_frames or 0)
+            out = np.empty(max(cap * n, 1), dtype=dt)
+        elif out.dtype != dt or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a C-contiguous {dt} array")
+        cap = out.size // max(n, 1) if cap_frames is None else min(cap_frames, out.size // max(n, 1))
+        nf, done = ctypes.c_uint64(), ctypes.c_int64()
+        _check(load().golhip_view_stream(self._h, nturns, every, ctypes.byref(v), _ptr(out), cap, ctypes.byref(nf),
+                                         ctypes.byref(done)))
+        return out.reshape(-1)[: nf.value * n].reshape(nf.value, v.out_h, v.out_w), done.value
+
     def perf(self) -> dict:
         p = Perf()
         _check(load().golhip_perf(self._h, ctypes.byref(p)))
@@ -467,6 +527,36 @@ def board_hash_np(words: np.ndarray, row0: int = 0) -> int:
         return int(z.sum(dtype=np.uint64))
 
 
+def view_frame_np(words: np.ndarray, width: int, height: int, x0: int = 0, y0: int = 0, scale: int = 1,
+                  out_w: int | None = None, out_h: int | None = None, fmt: int = VIEW_ARGB) -> np.ndarray:
+    """Host restatement of golhip_view_frame from canonical bit words
+    ((height, ceil(width / 32)) uint32): pixel (px, py) counts the alive cells
+    n of the scale x scale block from (x0 + px scale, y0 + py scale) on the
+    torus and stores g = (255 n + scale^2 - 1) // scale^2 (VIEW_GRAY8, uint8)
+    or g * 0x01010101 (VIEW_ARGB, uint32)."""
+    s = int(scale)
+    if s < 1:
+        raise ValueError("scale must be >= 1")
+    out_w = width // s if out_w is None else out_w
+    out_h = height // s if out_h is None else out_h
+    if not (0 <= x0 < width and 0 <= y0 < height and s >= 1 and out_w >= 1 and out_h >= 1
+            and out_w * s <= width and out_h * s <= height):
+        raise ValueError("view outside one lap of the board")
+    w = np.ascontiguousarray(words, dtype=np.uint32).reshape(height, -1)
+    ys = (y0 + np.arange(out_h * s)) % height
+    xs = (x0 + np.arange(out_w * s)) % width
+    n = np.zeros((out_h, out_w), dtype=np.int64)
+    band = max(1, (1 << 24) // max(out_w * s, 1) // s) * s  # rows unpacked at a time (whole pixel rows)
+    for r in range(0, out_h * s, band):
+        rows = w[ys[r:r + band]]
+        cells = ((rows[:, xs >> 5] >> (xs & 31).astype(np.uint32)) & np.uint32(1)).astype(np.uint8)
+        n[r // s:(r + cells.shape[0]) // s] = cells.reshape(-1, s, out_w, s).sum(axis=(1, 3), dtype=np.int64)
+    g = (255 * n + s * s - 1) // (s * s)
+    if fmt == VIEW_GRAY8:
+        return g.astype(np.uint8)
+    return (g * 0x01010101).astype(np.uint32)
+
+
 # --------------------------------------------------------------------------
 # host mirror of gol.Run (libgolhost.so, include/golrun.h)
 # --------------------------------------------------------------------------
@@ -506,6 +596,9 @@ def load_host(path: str = HOST_LIB_PATH) -> ctypes.CDLL:
     sig = {
         "golrun_last_error": ([], ctypes.c_char_p),
         "golrun_start": ([i64, i64, i64, i64, ctypes.c_char_p, i32, u32, i32, i32, P(ctypes.c_void_p)], ctypes.c_int),
+        "golrun_start_view": ([i64, i64, i64, i64, ctypes.c_char_p, i32, u32, i32, i32, P(View), i32,
+                               P(ctypes.c_void_p)], ctypes.c_int),
+        "golrun_view_frame": ([ctypes.c_void_p, ctypes.c_void_p, u64, P(i64)], ctypes.c_int),
         "golrun_event_string": ([P(RunEvent), ctypes.c_char_p, u64], ctypes.c_int),
         "golrun_next_event": ([ctypes.c_void_p, P(RunEvent), i32], ctypes.c_int),
         "golrun_event_cells": ([ctypes.c_void_p, ctypes.c_void_p, u64], ctypes.c_int),
@@ -529,13 +622,28 @@ class Run:
 
     def __init__(self, turns: int, threads: int, width: int, height: int, root: str, *, device: int = 0,
                  keys: bool = False, quirks: bool = False, cell_events: bool = True, turn_events: bool = True,
-                 events_cap: int = 0, ticker_ms: int = 0):
+                 events_cap: int = 0, ticker_ms: int = 0, view: dict | None = None):
+        """view: the live view (golrun_start_view), dict(scale=..., every=1,
+        x0=0, y0=0, out_w=None, out_h=None, fmt=VIEW_ARGB); missing out_w /
+        out_h are the largest that fit.  Run.view_frame() fetches frames."""
         lib = load_host()
         flags = (FLAG_KEYS if keys else 0) | (FLAG_REF_QUIRKS if quirks else 0) | \
             (0 if cell_events else FLAG_NO_CELL_EVENTS) | (0 if turn_events else FLAG_NO_TURN_EVENTS)
         h = ctypes.c_void_p()
-        rc = lib.golrun_start(turns, threads, width, height, root.encode(), device, flags, events_cap, ticker_ms,
-                              ctypes.byref(h))
+        self._view = None
+        if view is None:
+            rc = lib.golrun_start(turns, threads, width, height, root.encode(), device, flags, events_cap, ticker_ms,
+                                  ctypes.byref(h))
+        else:
+            unknown = set(view) - {"scale", "every", "x0", "y0", "out_w", "out_h", "fmt"}
+            if unknown or "scale" not in view:
+                raise ValueError(f"view needs scale; unknown keys {sorted(unknown)}")
+            s = int(view["scale"])
+            ow, oh = view.get("out_w"), view.get("out_h")
+            self._view = View(view.get("x0", 0), view.get("y0", 0), s, width // max(s, 1) if ow is None else ow,
+                              height // max(s, 1) if oh is None else oh, view.get("fmt", VIEW_ARGB))
+            rc = lib.golrun_start_view(turns, threads, width, height, root.encode(), device, flags, events_cap,
+                                       ticker_ms, ctypes.byref(self._view), int(view.get("every", 1)), ctypes.byref(h))
         if rc != 0:
             raise GolHipError(rc, lib.golrun_last_error().decode())
         self._h = h
@@ -590,6 +698,19 @@ class Run:
             raise GolHipError(rc, load_host().golrun_last_error().decode())
         counts = {EVENT_NAMES[k]: int(st.count[k]) for k in range(6)}
         return counts, st.last_turn, st.final_alive, flips[:turns_cap], dig[:turns_cap]
+
+    def view_frame(self):
+        """golrun_view_frame: (frame, turn), a copy of the newest published
+        frame ((out_h, out_w) uint32 or uint8) and the turn its pixels show."""
+        v = self._view
+        if v is None:
+            raise ValueError("the run was started without a view")
+        out = np.empty((v.out_h, v.out_w), dtype=np.uint8 if v.format == VIEW_GRAY8 else np.uint32)
+        t = ctypes.c_int64(-1)
+        rc = load_host().golrun_view_frame(self._h, _ptr(out), out.nbytes, ctypes.byref(t))
+        if rc != 0:
+            raise GolHipError(rc, load_host().golrun_last_error().decode())
+        return out, t.value
 
     def send_key(self, key: str) -> None:
         lib = load_host()

@@ -97,6 +97,8 @@ typedef struct golhip_perf {
     int64_t flip_resident_launches; /* flip-stream batches run as one resident launch
                                  (K5r, flip_overlap 2; round 6); their turns count in
                                  flip_launches, their time in flip_kernel_ms     */
+    int64_t view_frames;      /* frames rendered by the view kernels (K7)          */
+    double view_kernel_ms;    /* their summed device time (GOLHIP_FLAG_TIMING)   */
 } golhip_perf_t;
 
 /* ---- library ---------------------------------------------------------- */
@@ -326,6 +328,46 @@ int golhip_snapshot_rows(golhip_t h, int32_t row, int32_t nrows, uint32_t *out);
 /* Order-independent board digest: sum over words of
  * splitmix64((global_word_index << 32) | word) mod 2^64 (strips add up). */
 int golhip_board_hash(golhip_t h, uint64_t *hash);
+
+/* ---- live view -------------------------------------------------------- */
+/* A frame of the board for a window (the reference's sdl/window.go): out_w x
+ * out_h pixels, row-major, pixel (px, py) covering the s x s cells
+ *   x in [x0 + px s, x0 + px s + s) mod width,
+ *   y in [y0 + py s, y0 + py s + s) mod height.
+ * With n alive cells in that block, g = (255 n + s^2 - 1) / s^2 in integers:
+ * rounded up, so 0 only for an empty block (one glider shows at any scale)
+ * and 255 for a full one.  GRAY8 stores g, ARGB8888 stores g * 0x01010101; at
+ * s = 1 that is the pixel buffer of the reference's Window after its flips
+ * (FF FF FF FF or zeros) and the number of 0xFFFFFFFF pixels is its
+ * CountPixels().
+ * Required: 0 <= x0 < width, 0 <= y0 < height, 1 <= scale <=
+ * GOLHIP_VIEW_MAX_SCALE, out_w, out_h >= 1, out_w * scale <= width,
+ * out_h * scale <= height: at most one lap, which may cross the seam in x and
+ * in y.  On a strip handle y counts torus rows and [y0, y0 + out_h * scale)
+ * must lie inside the strip's rows (x still wraps).  The frame is rendered on
+ * the device from the board as it is stepped (no layout conversion, nothing
+ * of the board is written) and costs the same whatever the activity. */
+#define GOLHIP_VIEW_ARGB8888 0   /* uint32 per pixel, the SDL texture format of sdl/window.go:32 */
+#define GOLHIP_VIEW_GRAY8 1      /* uint8 per pixel (PGM-ready) */
+#define GOLHIP_VIEW_MAX_SCALE 1024
+typedef struct golhip_view {
+    int32_t x0, y0;        /* top-left cell of the viewport, torus coordinates */
+    int32_t scale;         /* s >= 1: one pixel covers s x s cells */
+    int32_t out_w, out_h;  /* frame size in pixels */
+    int32_t format;        /* GOLHIP_VIEW_* */
+} golhip_view_t;
+/* The frame of the current board (synchronous; *at_turn, nullable, is the turn
+ * it shows).  GOLHIP_ERANGE when cap_bytes is smaller than the frame.  If out
+ * lies inside golhip_host_alloc memory the kernel writes it there itself. */
+int golhip_view_frame(golhip_t h, const golhip_view_t *v, void *out, uint64_t cap_bytes, int64_t *at_turn);
+/* golhip_step(h, nturns, 0) with a frame rendered behind every `every`-th turn
+ * on the handle's stream (no host synchronisation between turns): out
+ * receives floor(nturns / every) consecutive frames, *frames (nullable) their
+ * number, *turns_done (nullable) the turns advanced (nturns; turns after the
+ * last frame are stepped too).  GOLHIP_ERANGE, with nothing advanced, when the
+ * frames exceed cap_frames.  Returns after the last frame has landed. */
+int golhip_view_stream(golhip_t h, int64_t nturns, int64_t every, const golhip_view_t *v, void *out,
+                       uint64_t cap_frames, uint64_t *frames, int64_t *turns_done);
 
 /* ---- measurement ------------------------------------------------------ */
 int golhip_perf(golhip_t h, golhip_perf_t *out);

@@ -13,6 +13,8 @@
 
 #include <stdint.h>
 
+#include "golhip.h"
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -57,6 +59,23 @@ const char *golrun_last_error(void);
  * ticker_ms: AliveCellsCount period (<= 0: 2000 as distributor.go:285). */
 int golrun_start(int64_t turns, int64_t threads, int64_t width, int64_t height, const char *root, int32_t device,
                  uint32_t flags, int32_t events_cap, int32_t ticker_ms, golrun_t *out);
+/* golrun_start with a live view (the reference's SDL window as pixels): the
+ * run renders `view` (golhip.h, golhip_view_frame's pixels) on the device
+ * after every `every`-th turn (>= 1) and publishes the frame before that
+ * turn's TurnComplete is sent; the frame of turn 0 is there before the first
+ * event, the final board's before FinalTurnComplete.  With cell events on,
+ * frames are rendered between the flip-stream batches instead (each shows its
+ * batch's last turn).  Runs of more than one strip (GOL_STRIPS / GOL_NGPU)
+ * are refused: golrun_wait reports the message. */
+int golrun_start_view(int64_t turns, int64_t threads, int64_t width, int64_t height, const char *root,
+                      int32_t device, uint32_t flags, int32_t events_cap, int32_t ticker_ms,
+                      const golhip_view_t *view, int32_t every, golrun_t *out);
+/* Copy of the newest published frame and the turn its pixels show.  After
+ * TurnComplete{t} of a run with every = 1 that turn is >= t; while paused it
+ * stays at the paused turn; after FinalTurnComplete it is the final board.
+ * GOLHIP_ERANGE when cap_bytes is smaller than the frame, GOLHIP_EINVAL when
+ * the run has no view or nothing is published yet. */
+int golrun_view_frame(golrun_t r, void *out, uint64_t cap_bytes, int64_t *turn);
 /* 1 = event received, 0 = channel closed and drained, 2 = timeout (timeout_ms >= 0). */
 int golrun_next_event(golrun_t r, golrun_event_t *ev, int32_t timeout_ms);
 /* Alive list of the last FinalTurnComplete received (alive_len pairs X, Y). */

@@ -52,6 +52,13 @@ package gol
 // }
 // static gh_status gh_alive_count(golhip_t h, uint64_t *n, int64_t *t) { return gh_wrap(golhip_alive_count(h, n, t)); }
 // static gh_status gh_snapshot_bytes(golhip_t h, uint8_t *out) { return gh_wrap(golhip_snapshot_bytes(h, out)); }
+// static gh_status gh_view_frame(golhip_t h, const golhip_view_t *v, void *out, uint64_t cap, int64_t *turn) {
+//     return gh_wrap(golhip_view_frame(h, v, out, cap, turn));
+// }
+// static gh_status gh_view_stream(golhip_t h, int64_t t, int64_t every, const golhip_view_t *v, void *out, uint64_t cap,
+//                                 uint64_t *frames, int64_t *done) {
+//     return gh_wrap(golhip_view_stream(h, t, every, v, out, cap, frames, done));
+// }
 import "C"
 
 import (
@@ -79,6 +86,9 @@ type engine struct {
 	flips  []uint32       // a Go view of it
 	counts []uint64       // per-turn list lengths of the last flipStream
 	xy     []int32        // strips: one strip's flip pairs of a turn
+
+	framesP unsafe.Pointer // golhip_host_alloc buffer of view frames (ARGB8888)
+	frames  []uint32       // a Go view of it
 }
 
 // check turns a libgolhip status into the reference's fail-fast behaviour
@@ -147,6 +157,11 @@ func (e *engine) close() {
 		C.golhip_host_free(e.flipsP)
 		e.flipsP = nil
 		e.flips = nil
+	}
+	if e.framesP != nil {
+		C.golhip_host_free(e.framesP)
+		e.framesP = nil
+		e.frames = nil
 	}
 	for i, h := range e.hs {
 		if h != nil {
@@ -317,4 +332,59 @@ func (e *engine) snapshot() []byte {
 		check(C.gh_snapshot_bytes(h, (*C.uint8_t)(unsafe.Pointer(&out[e.row0[i]*e.width]))))
 	}
 	return out
+}
+
+// View is the window onto the board (golhip_view_t): Scale x Scale cells a
+// pixel from cell (X0, Y0) on, OutW x OutH ARGB8888 pixels (the texture format
+// of sdl/window.go:32).  At Scale 1 a frame is the pixel buffer of the
+// reference's Window after its flips.
+type View struct {
+	X0, Y0, Scale, OutW, OutH int
+}
+
+func (v View) c() C.golhip_view_t {
+	return C.golhip_view_t{x0: C.int32_t(v.X0), y0: C.int32_t(v.Y0), scale: C.int32_t(v.Scale),
+		out_w: C.int32_t(v.OutW), out_h: C.int32_t(v.OutH), format: C.GOLHIP_VIEW_ARGB8888}
+}
+
+// growFrames makes the page-locked frame buffer hold n frames of v (C memory
+// the view kernel writes itself, like the flip buffer).
+func (e *engine) growFrames(v View, n int) {
+	need := n * v.OutW * v.OutH
+	if need <= len(e.frames) {
+		return
+	}
+	if e.framesP != nil {
+		C.golhip_host_free(e.framesP)
+		e.framesP = nil
+		e.frames = nil
+	}
+	var p unsafe.Pointer
+	check(C.gh_host_alloc(C.uint64_t(need*4), &p))
+	e.framesP = p
+	e.frames = (*[1 << 32]uint32)(p)[:need:need]
+}
+
+// ViewFrame renders the current board through v and returns the pixels and
+// the turn they show; the slice is valid until the next view call.  One strip
+// only (a whole-torus handle).
+func (e *engine) ViewFrame(v View) ([]uint32, int) {
+	e.growFrames(v, 1)
+	cv := v.c()
+	var turn C.int64_t
+	check(C.gh_view_frame(e.hs[0], &cv, e.framesP, C.uint64_t(len(e.frames)*4), &turn))
+	return e.frames[:v.OutW*v.OutH], int(turn)
+}
+
+// ViewStream runs n turns with a frame behind every `every`-th and returns
+// the n / every frames, consecutive, each OutW*OutH pixels (frame i shows turn
+// (i+1)*every of the batch); the slice is valid until the next view call.
+func (e *engine) ViewStream(n int, every int, v View) []uint32 {
+	e.growFrames(v, n/every)
+	cv := v.c()
+	var frames C.uint64_t
+	var done C.int64_t
+	check(C.gh_view_stream(e.hs[0], C.int64_t(n), C.int64_t(every), &cv, e.framesP,
+		C.uint64_t(len(e.frames)/(v.OutW*v.OutH)), &frames, &done))
+	return e.frames[:int(frames)*v.OutW*v.OutH]
 }
