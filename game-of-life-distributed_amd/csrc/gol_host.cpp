@@ -145,9 +145,11 @@ struct Engine {
         const int strips = opt.strips >= 0 ? opt.strips : env_int("GOL_STRIPS", 0);
         int n = strips > 0 ? strips : std::max(1, ngpu);
         n = (int)std::min<int64_t>(n, hgt);
-        if (n > 1 && opt.view.scale > 0)
+        const bool view_strips = opt.view_strips >= 0 ? opt.view_strips != 0 : env_int("GOL_VIEW_STRIPS", 0) != 0;
+        if (n > 1 && opt.view.scale > 0 && !view_strips)
             throw std::runtime_error("live view: a run of " + std::to_string(n) +
-                                     " strips (GOL_STRIPS / GOL_NGPU) has no view; run it on one strip");
+                                     " strips (GOL_STRIPS / GOL_NGPU) has no view; run it on one strip"
+                                     " (or opt in: RunOptions::view_strips, GOL_VIEW_STRIPS=1)");
         if (n <= 1) {
             hs.push_back(nullptr);
             row0.push_back(0);
@@ -269,7 +271,8 @@ void Run(Params p, Chan<Event> *events, Chan<char32_t> *keyPresses, const RunOpt
     // Live view: frames land in the ring and are published by pointer.  With
     // cell events the turns keep the flip stream, in batches that end on the
     // frame turns, and golhip_view_frame renders between them; without, the
-    // batch itself is golhip_view_stream.
+    // batch itself is golhip_view_stream.  On row strips (view_strips) both
+    // are the group calls, which on one whole-torus handle are the same calls.
     const bool view_on = opt.view.scale > 0;
     if (view_on && (!opt.view_sink || opt.view_every < 1)) throw std::runtime_error("live view: no sink, or every < 1");
     const int64_t batch_turns = opt.batch_turns > 0 ? opt.batch_turns : (opt.cell_events ? 64 : 256);
@@ -279,7 +282,7 @@ void Run(Params p, Chan<Event> *events, Chan<char32_t> *keyPresses, const RunOpt
     auto view_now = [&] {
         int64_t at = 0;
         uint8_t *f = ring->slot(ring->half, 0);
-        check(golhip_view_frame(board.hs[0], &opt.view, f, ring->frame_bytes, &at));
+        check(golhip_group_view_frame(board.hs.data(), (int32_t)board.hs.size(), &opt.view, f, ring->frame_bytes, &at));
         opt.view_sink->publish(f, ring->frame_bytes, at);
         ring->half ^= 1;
     };
@@ -471,8 +474,9 @@ void Run(Params p, Chan<Event> *events, Chan<char32_t> *keyPresses, const RunOpt
                     // frame i of the batch shows turn t + (i + 1) * every
                     uint64_t nf = 0;
                     view_half = ring->half;
-                    check(golhip_view_stream(board.hs[0], want, opt.view_every, &opt.view, ring->slot(view_half, 0),
-                                             (uint64_t)ring->per_half, &nf, &done));
+                    check(golhip_group_view_stream(board.hs.data(), (int32_t)board.hs.size(), want, opt.view_every,
+                                                   &opt.view, ring->slot(view_half, 0), (uint64_t)ring->per_half, &nf,
+                                                   &done));
                     ring->half ^= 1;
                 } else if (opt.cell_events) {
                     int rc = board.flip_stream(want, fb, counts.data(), &done, &n);
@@ -630,6 +634,7 @@ int golrun_start_view(int64_t turns, int64_t threads, int64_t width, int64_t hei
     o.turn_events = (flags & GOLRUN_FLAG_NO_TURN_EVENTS) == 0;
     if (ticker_ms > 0) o.ticker_seconds = ticker_ms / 1000.0;
     golrun *r = new golrun((size_t)events_cap, (flags & GOLRUN_FLAG_KEYS) != 0);
+    if (flags & GOLRUN_FLAG_VIEW_STRIPS) o.view_strips = 1;
     if (view) {
         r->has_view = true;
         o.view = *view;

@@ -402,6 +402,10 @@ struct RunOptions {
     // turn 0's frame before the first event, the final board's before
     // FinalTurnComplete.  Off by default (scale 0).  One strip only.
     golhip_view_t view{0, 0, 0, 0, 0, GOLHIP_VIEW_ARGB8888};
+    // A view of a run on more than one strip (golhip_group_view_frame /
+    // golhip_group_view_stream) is opt-in: 1 on, 0 off (such a run is refused),
+    // -1 from the environment, GOL_VIEW_STRIPS=1 (unset: off).
+    int view_strips = -1;
     int64_t view_every = 1;
     ViewSink *view_sink = nullptr;
 };

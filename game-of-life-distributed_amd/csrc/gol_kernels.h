@@ -270,8 +270,28 @@ struct ViewArgs {
     int il;        // 0 canonical, 2 pairs, 4 quads
     int format;    // GOLHIP_VIEW_*
     int ngr, gfirst, vec, pb;  // set by launch_view
+    int r_lo, r_hi;            // counts mode only (launch_view_counts)
 };
 hipError_t launch_view(ViewArgs a, hipStream_t s);
+// Counts mode, for a pixel row that straddles row strips: the alive counts of
+// rows [r_lo, r_hi) of the s rows of one pixel row, uint32 per pixel, to the
+// 16-byte aligned row `out` of view_count_stride(out_w) words.  y0 is the local
+// row of the pixel row's row 0 and may lie outside [0, H); the rows read,
+// [y0 + r_lo, y0 + r_hi), must not.  out_h is taken as 1.
+hipError_t launch_view_counts(ViewArgs a, hipStream_t s);
+constexpr int kViewCountAlign = 16;  // pixels a count row is padded to (one lane's pixels in any format)
+int view_count_stride(int out_w);
+// Pixel rows from their count rows: row j < nrows of the table is pixel row
+// py[j] of the frame `out`, the sum of the k[j] rows of `counts` (stride cw
+// words) from row slot[j] on, normalised as launch_view's pixels are.
+constexpr int kViewResolveRows = 32;
+struct ViewResolveArgs {
+    const uint32_t *counts;
+    void *out;
+    int cw, out_w, s, format, vec, nrows;
+    int py[kViewResolveRows], slot[kViewResolveRows], k[kViewResolveRows];
+};
+hipError_t launch_view_resolve(ViewResolveArgs a, hipStream_t s);
 
 // "NAME=value ..." of the build's tuning macros (golhip_build_info).
 const char *build_info();

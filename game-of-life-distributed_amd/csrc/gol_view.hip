@@ -20,6 +20,15 @@
 // Pixels are stored once each, 16 B a lane where the frame allows, else one
 // pixel a store: the frame may be host memory, so no atomics and no
 // read-modify-write on it.
+//
+// A board held as row strips (golhip_group_view_frame): a pixel row whose s
+// board rows lie in one strip is rendered by that strip with the kernels above.
+// A pixel row that straddles strips is rendered in pieces: every strip runs
+// its kernel in counts mode (template parameter COUNTS) over the rows
+// [r_lo, r_hi) of the pixel row that it holds and stores the raw alive counts,
+// uint32 a pixel, to a row of a device buffer; gol_view_resolve_kernel sums
+// the k >= 2 count rows of each such pixel row, normalises and stores the
+// pixels.  The masks and the x-seam logic do not know about the pieces.
 #include "gol_kernels.h"
 #include "gol_layout.h"
 
@@ -187,9 +196,13 @@ struct RowCursor {
 };
 
 // s < 32.  One thread: Pixel::kPer16 consecutive pixels of one pixel row.
-template <int IL, int FORMAT>
+// COUNTS: rows [a.r_lo, a.r_hi) of the one pixel row whose row 0 is local row
+// a.y0 (which may lie outside the strip; the rows read do not), raw counts to
+// the uint32 row a.out (4 a lane: FORMAT is ARGB8888).
+template <int IL, int FORMAT, bool COUNTS = false>
 __global__ __launch_bounds__(kViewThreads) void gol_view_small_kernel(ViewArgs a) {
     constexpr int G = Pixel<FORMAT>::kPer16;
+    static_assert(!COUNTS || G == 4, "counts mode stores one uint4 a lane");
     const int64_t t = (int64_t)blockIdx.x * kViewThreads + threadIdx.x;
     const int ngx = (a.out_w + G - 1) / G;
     const int py = (int)(t / ngx);
@@ -201,11 +214,16 @@ __global__ __launch_bounds__(kViewThreads) void gol_view_small_kernel(ViewArgs a
     if (xs64 >= a.W) xs64 -= a.W;
     const int xs = (int)xs64;
     int yy = a.y0 + py * s;  // < 2 H
-    if (yy >= a.H) yy -= a.H;
+    if constexpr (COUNTS) {
+        yy = a.y0 + a.r_lo;
+    } else {
+        if (yy >= a.H) yy -= a.H;
+    }
+    const int nr = COUNTS ? a.r_hi - a.r_lo : s;
     uint32_t acc[G];
 #pragma unroll
     for (int p = 0; p < G; ++p) acc[p] = 0;
-    for (int r = 0; r < s; ++r) {
+    for (int r = 0; r < nr; ++r) {
         RowCursor<IL> cur;
         int off = cur.begin(a.rows + (int64_t)yy * a.Ww, a.W, a.Ww, xs);
         uint32_t lo = cur.next(), hi = cur.next();
@@ -220,13 +238,18 @@ __global__ __launch_bounds__(kViewThreads) void gol_view_small_kernel(ViewArgs a
                 hi = cur.next();
             }
         }
-        if (++yy == a.H) yy = 0;
+        if (++yy == a.H) yy = 0;  // never in counts mode: a piece lies inside the strip
     }
-    const uint32_t s2 = (uint32_t)(s * s);
-    uint32_t g[G];
+    if constexpr (COUNTS) {
+        // the count row is padded to kViewCountAlign pixels: always one 16-byte store
+        *reinterpret_cast<uint4 *>(static_cast<uint32_t *>(a.out) + px0) = make_uint4(acc[0], acc[1], acc[2], acc[3]);
+    } else {
+        const uint32_t s2 = (uint32_t)(s * s);
+        uint32_t g[G];
 #pragma unroll
-    for (int p = 0; p < G; ++p) g[p] = gray_of(acc[p], s2);
-    store_pixels<FORMAT>(a.out, (int64_t)py * a.out_w + px0, g, min(G, a.out_w - px0), a.vec != 0);
+        for (int p = 0; p < G; ++p) g[p] = gray_of(acc[p], s2);
+        store_pixels<FORMAT>(a.out, (int64_t)py * a.out_w + px0, g, min(G, a.out_w - px0), a.vec != 0);
+    }
 }
 
 // s >= 32.  One block: pixels [p0, p0 + np) of one pixel row (np <= a.pb <=
@@ -234,7 +257,8 @@ __global__ __launch_bounds__(kViewThreads) void gol_view_small_kernel(ViewArgs a
 // Group k of the walk that starts at the viewport's first group (a.gfirst) is
 // group (a.gfirst + k) mod a.ngr of a row, on lap (a.gfirst + k) / a.ngr, and
 // starts at column lap * W + 32 * words * index of the unrolled torus.
-template <int IL, int FORMAT>
+// COUNTS: as in gol_view_small_kernel.
+template <int IL, int FORMAT, bool COUNTS = false>
 __global__ __launch_bounds__(kViewThreads) void gol_view_kernel(ViewArgs a) {
     constexpr int GW = Group<IL>::kWords, GB = Group<IL>::kBits;
     constexpr int NSEG = GW + 1;  // pixels one group can touch (s >= 32)
@@ -254,7 +278,12 @@ __global__ __launch_bounds__(kViewThreads) void gol_view_kernel(ViewArgs a) {
     };
     const int k_lo = walk_of(a.x0 + rel_lo), k_hi = walk_of(a.x0 + rel_hi - 1);
     int y_first = a.y0 + py * s;  // < 2 H
-    if (y_first >= a.H) y_first -= a.H;
+    if constexpr (COUNTS) {
+        y_first = a.y0 + a.r_lo;
+    } else {
+        if (y_first >= a.H) y_first -= a.H;
+    }
+    const int nr = COUNTS ? a.r_hi - a.r_lo : s;
 
     for (int k = k_lo + (int)threadIdx.x; k <= k_hi; k += kViewThreads) {
         const int gk = a.gfirst + k;
@@ -275,7 +304,7 @@ __global__ __launch_bounds__(kViewThreads) void gol_view_kernel(ViewArgs a) {
         int yy = y_first;
         const uint32_t *row = a.rows + (int64_t)yy * a.Ww;
 #pragma unroll 4
-        for (int r = 0; r < s; ++r) {
+        for (int r = 0; r < nr; ++r) {
             uint32_t w[GW];
             load_group<IL>(row, gi, w);
 #pragma unroll
@@ -292,14 +321,53 @@ __global__ __launch_bounds__(kViewThreads) void gol_view_kernel(ViewArgs a) {
     __syncthreads();
 
     constexpr int G = Pixel<FORMAT>::kPer16;
-    const uint32_t s2 = (uint32_t)(s * s);
-    const int64_t base = (int64_t)py * a.out_w + p0;
-    for (int u = threadIdx.x * G; u < np; u += kViewThreads * G) {
-        uint32_t g[G];
+    if constexpr (COUNTS) {
+        // p0 and u are multiples of 4 and the count row is padded: 16-byte stores
+        uint32_t *o = static_cast<uint32_t *>(a.out) + p0;
+        for (int u = threadIdx.x * 4; u < np; u += kViewThreads * 4) {
+            uint32_t c[4];
 #pragma unroll
-        for (int p = 0; p < G; ++p) g[p] = u + p < np ? gray_of(pix[u + p], s2) : 0u;
-        store_pixels<FORMAT>(a.out, base + u, g, min(G, np - u), a.vec != 0);
+            for (int p = 0; p < 4; ++p) c[p] = u + p < np ? pix[u + p] : 0u;
+            *reinterpret_cast<uint4 *>(o + u) = make_uint4(c[0], c[1], c[2], c[3]);
+        }
+    } else {
+        const uint32_t s2 = (uint32_t)(s * s);
+        const int64_t base = (int64_t)py * a.out_w + p0;
+        for (int u = threadIdx.x * G; u < np; u += kViewThreads * G) {
+            uint32_t g[G];
+#pragma unroll
+            for (int p = 0; p < G; ++p) g[p] = u + p < np ? gray_of(pix[u + p], s2) : 0u;
+            store_pixels<FORMAT>(a.out, base + u, g, min(G, np - u), a.vec != 0);
+        }
     }
+}
+
+// Pixel rows that straddle strips: block row j sums the a.k[j] count rows from
+// row a.slot[j] of a.counts on and stores pixel row a.py[j] of the frame.  One
+// thread: Pixel::kPer16 consecutive pixels.
+template <int FORMAT>
+__global__ __launch_bounds__(kViewThreads) void gol_view_resolve_kernel(ViewResolveArgs a) {
+    constexpr int G = Pixel<FORMAT>::kPer16;
+    const int j = blockIdx.y;
+    const int px0 = (int)(blockIdx.x * kViewThreads + threadIdx.x) * G;
+    if (px0 >= a.out_w) return;
+    uint32_t acc[G];
+#pragma unroll
+    for (int p = 0; p < G; ++p) acc[p] = 0;
+    const uint32_t *c = a.counts + (int64_t)a.slot[j] * a.cw + px0;  // px0 + G <= cw (kViewCountAlign)
+    for (int i = 0; i < a.k[j]; ++i) {
+#pragma unroll
+        for (int q = 0; q < G / 4; ++q) {
+            const uint4 v = reinterpret_cast<const uint4 *>(c)[q];
+            acc[4 * q] += v.x, acc[4 * q + 1] += v.y, acc[4 * q + 2] += v.z, acc[4 * q + 3] += v.w;
+        }
+        c += a.cw;
+    }
+    const uint32_t s2 = (uint32_t)(a.s * a.s);
+    uint32_t g[G];
+#pragma unroll
+    for (int p = 0; p < G; ++p) g[p] = gray_of(acc[p], s2);
+    store_pixels<FORMAT>(a.out, (int64_t)a.py[j] * a.out_w + px0, g, min(G, a.out_w - px0), a.vec != 0);
 }
 
 template <int IL, int FORMAT>
@@ -317,7 +385,65 @@ hipError_t launch_view_t(const ViewArgs &a, hipStream_t st) {
     return hipGetLastError();
 }
 
+template <int IL>
+hipError_t launch_counts_t(const ViewArgs &a, hipStream_t st) {
+    constexpr int F = GOLHIP_VIEW_ARGB8888;
+    if (a.s < 32) {
+        const int blocks = ((a.out_w + 3) / 4 + kViewThreads - 1) / kViewThreads;
+        hipLaunchKernelGGL((gol_view_small_kernel<IL, F, true>), dim3((unsigned)blocks), dim3(kViewThreads), 0, st, a);
+    } else {
+        const int blocks = (a.out_w + a.pb - 1) / a.pb;
+        hipLaunchKernelGGL((gol_view_kernel<IL, F, true>), dim3((unsigned)blocks), dim3(kViewThreads), 0, st, a);
+    }
+    return hipGetLastError();
+}
+
+// The fields of ViewArgs that the launchers derive.
+bool view_derive(ViewArgs &a) {
+    const int gw = a.il == 0 ? 1 : a.il, gb = 32 * gw;
+    if (!(a.il == 0 || a.il == 2 || a.il == 4) || a.Ww % gw != 0 || (a.il != 0 && a.W % gb != 0)) return false;
+    a.ngr = a.Ww / gw;
+    a.gfirst = a.x0 / gb;
+    // gol_view_kernel: about one group column per thread, whole 16-byte units per block
+    a.pb = (int)std::min<int64_t>(kViewMaxPix, std::max<int64_t>(16, ((int64_t)kViewThreads * gb / a.s) / 16 * 16));
+    return true;
+}
+
 }  // namespace
+
+int view_count_stride(int out_w) { return (out_w + kViewCountAlign - 1) / kViewCountAlign * kViewCountAlign; }
+
+hipError_t launch_view_counts(ViewArgs a, hipStream_t st) {
+    if (!view_derive(a)) return hipErrorInvalidValue;
+    // the rows read are rows of the strip; one pixel row; an aligned count row
+    if (a.r_lo < 0 || a.r_hi > a.s || a.r_lo >= a.r_hi || a.y0 + a.r_lo < 0 || a.y0 + a.r_hi > a.H ||
+        (uintptr_t)a.out % 16 != 0 || a.out_w < 1)
+        return hipErrorInvalidValue;
+    a.out_h = 1;
+    a.vec = 1;
+    switch (a.il) {
+    case 0:
+        return launch_counts_t<0>(a, st);
+    case 2:
+        return launch_counts_t<2>(a, st);
+    default:
+        return launch_counts_t<4>(a, st);
+    }
+}
+
+hipError_t launch_view_resolve(ViewResolveArgs a, hipStream_t st) {
+    if (a.nrows < 1 || a.nrows > kViewResolveRows || a.cw != view_count_stride(a.out_w) ||
+        (uintptr_t)a.counts % 16 != 0)
+        return hipErrorInvalidValue;
+    const int per16 = a.format == GOLHIP_VIEW_GRAY8 ? 16 : 4;
+    a.vec = ((uintptr_t)a.out % 16 == 0 && a.out_w % per16 == 0) ? 1 : 0;
+    const dim3 grid((unsigned)(((a.out_w + per16 - 1) / per16 + kViewThreads - 1) / kViewThreads), (unsigned)a.nrows);
+    if (a.format == GOLHIP_VIEW_GRAY8)
+        hipLaunchKernelGGL((gol_view_resolve_kernel<GOLHIP_VIEW_GRAY8>), grid, dim3(kViewThreads), 0, st, a);
+    else
+        hipLaunchKernelGGL((gol_view_resolve_kernel<GOLHIP_VIEW_ARGB8888>), grid, dim3(kViewThreads), 0, st, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_view(ViewArgs a, hipStream_t st) {
     const int gw = a.il == 0 ? 1 : a.il, gb = 32 * gw;

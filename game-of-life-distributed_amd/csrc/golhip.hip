@@ -41,16 +41,20 @@ struct HostBuf {
     uintptr_t base;
     size_t bytes;
     void *dev;  // device address of base
+    int device; // the device it was mapped on
 };
 std::mutex g_host_mu;
 std::vector<HostBuf> g_host_bufs;
 
 // Device address of [p, p + bytes) if it lies inside one golhip_host_alloc buffer.
-void *mapped_device_ptr(const void *p, size_t bytes) {
+void *mapped_device_ptr(const void *p, size_t bytes, int *device = nullptr) {
     std::lock_guard<std::mutex> g(g_host_mu);
     const uintptr_t a = (uintptr_t)p;
     for (const HostBuf &b : g_host_bufs)
-        if (a >= b.base && a + bytes <= b.base + b.bytes) return (char *)b.dev + (a - b.base);
+        if (a >= b.base && a + bytes <= b.base + b.bytes) {
+            if (device) *device = b.device;
+            return (char *)b.dev + (a - b.base);
+        }
     return nullptr;
 }
 
@@ -207,6 +211,8 @@ struct golhip {
     double flip_ms = 0;
     uint8_t *d_stage = nullptr;  // byte staging for load/snapshot
     int64_t stage_cap = 0;
+    uint32_t *d_vcount = nullptr;  // group view: count rows of the pixel rows that straddle strips
+    int64_t vcount_cap = 0;
     bool flips_valid = false;
     int64_t flips_turn = -1;
 
@@ -1776,8 +1782,10 @@ int golhip_host_alloc(uint64_t bytes, void **out) {
         (void)hipHostFree(p);
         return fail(GOLHIP_EHIP, "hipHostGetDevicePointer: %s", hipGetErrorString(e));
     }
+    int device = 0;
+    (void)hipGetDevice(&device);
     std::lock_guard<std::mutex> g(g_host_mu);
-    g_host_bufs.push_back({(uintptr_t)p, (size_t)bytes, d});
+    g_host_bufs.push_back({(uintptr_t)p, (size_t)bytes, d, device});
     *out = p;
     return GOLHIP_OK;
 }
@@ -1882,6 +1890,7 @@ int golhip_destroy(golhip_t h) {
     HIP_RC(hipFree(h->d_ftdone));
     HIP_RC(hipFree(h->d_ev));
     HIP_RC(hipFree(h->d_stage));
+    HIP_RC(hipFree(h->d_vcount));
     HIP_RC(hipFree(h->d_sync));
     HIP_RC(hipFree(h->d_trace));
     HIP_RC(hipFree(h->backup));
@@ -2402,8 +2411,9 @@ namespace {
 // process, halos moved by peer copies; want_flips keeps every strip's flip
 // list of the last turn (golhip_flips, global coordinates, strip order =
 // row-major order of the board).
-int group_step_impl(golhip_t *hs, int32_t n, int64_t nturns, int32_t want_flips) {
-    if (!hs || n < 1 || nturns < 0) return fail(GOLHIP_EINVAL, "bad group");
+// The strips of a group: one board, contiguous from row 0, covering it.
+int group_check(golhip_t *hs, int32_t n) {
+    if (!hs || n < 1) return fail(GOLHIP_EINVAL, "bad group");
     for (int i = 0; i < n; ++i) {
         if (int rc = check(hs[i])) return rc;
         if (!hs[i]->loaded) return fail(GOLHIP_EINVAL, "strip %d has no board", i);
@@ -2413,13 +2423,22 @@ int group_step_impl(golhip_t *hs, int32_t n, int64_t nturns, int32_t want_flips)
         if (hs[i]->row0 != expect_row0) return fail(GOLHIP_EINVAL, "strip %d starts at %d, expected %d", i, hs[i]->row0, expect_row0);
     }
     if (hs[n - 1]->row0 + hs[n - 1]->rows != hs[0]->H) return fail(GOLHIP_EINVAL, "strips do not cover the board");
-    std::vector<std::unique_lock<std::mutex>> locks;
-    for (int i = 0; i < n; ++i) locks.emplace_back(hs[i]->mu);
+    return GOLHIP_OK;
+}
+
+// The step of a checked group with every strip's mutex held.  `keep`
+// (golhip_group_view_stream): the caller's n events, left alive, and no
+// synchronisation at the end: the caller synchronises every stream and takes
+// the skew flags itself.
+int group_step_locked(golhip_t *hs, int32_t n, int64_t nturns, int32_t want_flips, hipEvent_t *keep = nullptr) {
     std::vector<hipEvent_t> ready(n, nullptr);
     int rc = GOLHIP_OK;
     for (int i = 0; i < n; ++i) {
         HIP_RC(hipSetDevice(hs[i]->device));
-        HIP_RC(hipEventCreateWithFlags(&ready[i], hipEventDisableTiming));
+        if (keep)
+            ready[i] = keep[i];
+        else
+            HIP_RC(hipEventCreateWithFlags(&ready[i], hipEventDisableTiming));
         if (!rc && want_il(hs[i]) != want_il(hs[0])) rc = fail(GOLHIP_EINVAL, "strip %d uses another word layout", i);
         if (!rc) rc = set_layout(hs[i], want_il(hs[i]));
         hs[i]->flips_valid = false;
@@ -2491,7 +2510,7 @@ int group_step_impl(golhip_t *hs, int32_t n, int64_t nturns, int32_t want_flips)
             if (!rc) rc = start_flips(hs[i]);
         }
     }
-    for (int i = 0; i < n; ++i) {
+    for (int i = 0; i < n && !keep; ++i) {
         HIP_RC(hipSetDevice(hs[i]->device));
         if (ready[i]) {
             HIP_RC(hipStreamSynchronize(hs[i]->stream));
@@ -2500,6 +2519,14 @@ int group_step_impl(golhip_t *hs, int32_t n, int64_t nturns, int32_t want_flips)
         if (!rc) rc = take_skew_err(hs[i]);
     }
     return rc;
+}
+
+int group_step_impl(golhip_t *hs, int32_t n, int64_t nturns, int32_t want_flips) {
+    if (nturns < 0) return fail(GOLHIP_EINVAL, "bad group");
+    if (int rc = group_check(hs, n)) return rc;
+    std::vector<std::unique_lock<std::mutex>> locks;
+    for (int i = 0; i < n; ++i) locks.emplace_back(hs[i]->mu);
+    return group_step_locked(hs, n, nturns, want_flips);
 }
 }  // namespace
 
@@ -2821,6 +2848,377 @@ int golhip_view_stream(golhip_t h, int64_t nturns, int64_t every, const golhip_v
         if (int rc = sync_stream(h)) return rc;
     if (frames) *frames = nf;
     if (turns_done) *turns_done = h->turns - turns0;
+    return GOLHIP_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// ---------------------------------------------------------------------------
+// live view of a board held as n row strips (golhip_group_view_*)
+// ---------------------------------------------------------------------------
+// The viewport's rows, one lap at most, cut at the strip boundaries.  A run of
+// whole pixel rows inside one strip is a Whole: the strip renders it straight
+// into the frame.  What is left of a strip's run at either end is a Part: rows
+// [r_lo, r_hi) of pixel row py, rendered as a count row (slot `slot` of the
+// seam buffer).  The parts of one pixel row are consecutive and take
+// consecutive slots; a SeamRow lists them.  A strip has at most two runs (the
+// viewport ends in the strip it began in), so at most two Wholes, four Parts.
+struct ViewWhole {
+    int strip, py, npy, ylocal;  // ylocal: the strip's local row of pixel row py's row 0
+};
+struct ViewPart {
+    int strip, py, r_lo, r_hi, ylocal, slot;
+};
+struct ViewSeamRow {
+    int py, slot, k;
+};
+struct GroupViewPlan {
+    std::vector<ViewWhole> wholes;
+    std::vector<ViewPart> parts;
+    std::vector<ViewSeamRow> seams;
+    int first = 0;   // the strip that holds row y0: it resolves
+    int cw = 0;      // words of a count row
+    uint64_t bpp = 4, bytes = 0;
+};
+
+void group_view_plan(golhip_t *hs, int n, const golhip_view_t *v, GroupViewPlan *p) {
+    const int s = v->scale;
+    int i = 0;
+    while (!(v->y0 >= hs[i]->row0 && v->y0 < hs[i]->row0 + hs[i]->rows)) ++i;
+    p->first = i;
+    p->cw = golk::view_count_stride(v->out_w);
+    p->bpp = v->format == GOLHIP_VIEW_GRAY8 ? 1 : 4;
+    p->bytes = (uint64_t)v->out_w * (uint64_t)v->out_h * p->bpp;
+    int64_t rel = 0, left = (int64_t)v->out_h * s;
+    int cur = v->y0;
+    while (left > 0) {
+        const int64_t end = rel + std::min<int64_t>(left, hs[i]->row0 + hs[i]->rows - cur);  // this run: [rel, end)
+        int64_t r = rel;
+        auto local = [&](int64_t at) { return (int)(cur - hs[i]->row0 + (at - rel)); };  // local row of view row `at`
+        if (r % s != 0) {  // the end of a pixel row begun in the strip before
+            const int py = (int)(r / s);
+            const int64_t hi = std::min<int64_t>(end, (int64_t)(py + 1) * s);
+            p->parts.push_back({i, py, (int)(r - (int64_t)py * s), (int)(hi - (int64_t)py * s), local((int64_t)py * s), 0});
+            r = hi;
+        }
+        if (const int npy = (int)((end - r) / s)) {
+            p->wholes.push_back({i, (int)(r / s), npy, local(r)});
+            r += (int64_t)npy * s;
+        }
+        if (r < end) {  // the start of a pixel row that the next strip goes on with
+            p->parts.push_back({i, (int)(r / s), 0, (int)(end - r), local(r), 0});
+        }
+        left -= end - rel;
+        cur += (int)(end - rel);
+        rel = end;
+        if (cur == hs[i]->row0 + hs[i]->rows) {  // on into the next strip, past the last into the first
+            i = (i + 1) % n;
+            cur = hs[i]->row0;
+        }
+    }
+    for (size_t j = 0; j < p->parts.size(); ++j) {
+        p->parts[j].slot = (int)j;
+        if (p->seams.empty() || p->seams.back().py != p->parts[j].py)
+            p->seams.push_back({p->parts[j].py, (int)j, 1});
+        else
+            p->seams.back().k++;
+    }
+}
+
+int ensure_vcount(golhip_t h, int64_t words) {
+    if (h->vcount_cap >= words) return GOLHIP_OK;
+    if (h->d_vcount) HIP_OR_FAIL(hipFree(h->d_vcount));
+    h->d_vcount = nullptr;
+    h->vcount_cap = 0;
+    HIP_OR_FAIL(hipMalloc(&h->d_vcount, (size_t)words * sizeof(uint32_t)));
+    h->vcount_cap = words;
+    return GOLHIP_OK;
+}
+
+// Checks of both group view calls, before any mutex is taken (as
+// group_step_impl reads its strips); *torus: the group is one whole-torus
+// handle and the call is the single-handle one.
+int group_view_check(golhip_t *hs, int32_t n, const golhip_view_t *v, bool *torus) {
+    if (int rc = group_check(hs, n)) return rc;
+    *torus = n == 1 && hs[0]->torus();
+    if (*torus) return GOLHIP_OK;
+    for (int i = 0; i < n; ++i) {
+        if (hs[i]->turns != hs[0]->turns)
+            return fail(GOLHIP_EINVAL, "strip %d is at turn %lld, strip 0 at turn %lld", i, (long long)hs[i]->turns,
+                        (long long)hs[0]->turns);
+        if (want_il(hs[i]) != want_il(hs[0])) return fail(GOLHIP_EINVAL, "strip %d uses another word layout", i);
+    }
+    if (!v) return fail(GOLHIP_EINVAL, "view is null");
+    // view_check's rules on the whole torus
+    const int W = hs[0]->W, H = hs[0]->H;
+    if (v->format != GOLHIP_VIEW_ARGB8888 && v->format != GOLHIP_VIEW_GRAY8)
+        return fail(GOLHIP_EINVAL, "view format %d", v->format);
+    if (v->scale < 1 || v->scale > GOLHIP_VIEW_MAX_SCALE)
+        return fail(GOLHIP_EINVAL, "view scale %d not in [1, %d]", v->scale, GOLHIP_VIEW_MAX_SCALE);
+    if (v->out_w < 1 || v->out_h < 1) return fail(GOLHIP_EINVAL, "view frame %d x %d", v->out_w, v->out_h);
+    if (v->x0 < 0 || v->x0 >= W || v->y0 < 0 || v->y0 >= H)
+        return fail(GOLHIP_EINVAL, "view origin (%d, %d) outside the %d x %d board", v->x0, v->y0, W, H);
+    if ((int64_t)v->out_w * v->scale > W || (int64_t)v->out_h * v->scale > H)
+        return fail(GOLHIP_EINVAL, "view of %d x %d pixels at scale %d is more than one lap of the %d x %d board",
+                    v->out_w, v->out_h, v->scale, W, H);
+    return GOLHIP_OK;
+}
+
+// Events of one group view call: part[i] after strip i's count rows have
+// reached the seam buffer, `resolved` after the resolve kernel has read them.
+struct GroupViewEvents {
+    std::vector<hipEvent_t> part;
+    hipEvent_t resolved = nullptr;
+    bool resolved_set = false;
+};
+
+golk::ViewArgs group_view_args(golhip_t h, const golhip_view_t *v) {
+    golk::ViewArgs a{};
+    a.rows = h->cur_rows();
+    a.W = h->W;
+    a.Ww = h->Ww;
+    a.H = h->rows;
+    a.x0 = v->x0;
+    a.s = v->scale;
+    a.out_w = v->out_w;
+    a.il = h->il;
+    a.format = v->format;
+    return a;
+}
+
+// Start / end of a timed span of view kernels on h's stream (GOLHIP_FLAG_TIMING).
+int view_span_begin(golhip_t h, hipEvent_t *e0, hipEvent_t *e1) {
+    *e0 = *e1 = nullptr;
+    if (!(h->flags & GOLHIP_FLAG_TIMING)) return GOLHIP_OK;
+    *e0 = take_event(h);
+    *e1 = take_event(h);
+    if (!*e0 || !*e1) return fail(GOLHIP_EHIP, "hipEventCreate failed");
+    HIP_OR_FAIL(hipEventRecord(*e0, h->stream));
+    return GOLHIP_OK;
+}
+int view_span_end(golhip_t h, hipEvent_t e0, hipEvent_t e1) {
+    if (!e1) return GOLHIP_OK;
+    HIP_OR_FAIL(hipEventRecord(e1, h->stream));
+    h->ev_pending.push_back({e0, e1, 4});
+    if (h->ev_pending.size() >= 4096) return drain_events(h);
+    return GOLHIP_OK;
+}
+
+// Enqueue one frame of the strips' current boards to `out` (host; `mapped`:
+// its device address in golhip_host_alloc memory mapped on `mapped_dev`, or
+// null).  Every strip's mutex is held; nothing is synchronised.
+int group_view_enqueue(golhip_t *hs, int n, const golhip_view_t *v, const GroupViewPlan &p, GroupViewEvents &ev,
+                       void *out, void *mapped, int mapped_dev) {
+    golhip *res = hs[p.first];
+    const int64_t row_bytes = (int64_t)v->out_w * (int64_t)p.bpp;
+    const int64_t seam_words = (int64_t)p.parts.size() * p.cw;
+    if (seam_words) {
+        if (int rc = set_dev(res)) return rc;
+        if (int rc = ensure_vcount(res, seam_words)) return rc;
+    }
+    for (int i = 0; i < n; ++i) {
+        golhip *h = hs[i];
+        bool any = false, any_part = false;
+        for (const ViewWhole &w : p.wholes) any |= w.strip == i;
+        for (const ViewPart &q : p.parts) any_part |= q.strip == i;
+        if (!any && !any_part) continue;
+        if (int rc = set_dev(h)) return rc;
+        const bool direct = mapped && h->device == mapped_dev;
+        // staging: this strip's whole pixel rows, then (the resolving strip) the seam rows
+        int64_t stage_bytes = 0;
+        std::vector<int64_t> whole_off;
+        for (const ViewWhole &w : p.wholes)
+            if (w.strip == i) {
+                whole_off.push_back(stage_bytes);
+                stage_bytes += ((int64_t)w.npy * row_bytes + 15) / 16 * 16;
+            }
+        if (i == p.first) stage_bytes += (int64_t)p.seams.size() * row_bytes;
+        if (!direct)
+            if (int rc = ensure_stage(h, std::max<int64_t>(stage_bytes, 16))) return rc;
+        const bool peer = any_part && h->device != res->device;  // count rows travel to the resolving strip's device
+        if (peer)
+            if (int rc = ensure_vcount(h, seam_words)) return rc;
+        // the seam buffer is reused from frame to frame: no count row of this
+        // frame before the last frame's resolve has read the buffer
+        if (any_part && i != p.first && ev.resolved_set) HIP_OR_FAIL(hipStreamWaitEvent(h->stream, ev.resolved, 0));
+        hipEvent_t e0, e1;
+        if (int rc = view_span_begin(h, &e0, &e1)) return rc;
+        for (const ViewPart &q : p.parts) {
+            if (q.strip != i) continue;
+            golk::ViewArgs a = group_view_args(h, v);
+            uint32_t *dst = (peer ? h->d_vcount : res->d_vcount) + (int64_t)q.slot * p.cw;
+            a.out = dst;
+            a.y0 = q.ylocal;
+            a.out_h = 1;
+            a.r_lo = q.r_lo;
+            a.r_hi = q.r_hi;
+            const hipError_t e = golk::launch_view_counts(a, h->stream);
+            if (e != hipSuccess) return fail(GOLHIP_EHIP, "view counts launch (strip %d): %s", i, hipGetErrorString(e));
+            if (peer)
+                HIP_OR_FAIL(hipMemcpyPeerAsync(res->d_vcount + (int64_t)q.slot * p.cw, res->device, dst, h->device,
+                                               (size_t)p.cw * sizeof(uint32_t), h->stream));
+        }
+        size_t wi = 0;
+        for (const ViewWhole &w : p.wholes) {
+            if (w.strip != i) continue;
+            golk::ViewArgs a = group_view_args(h, v);
+            a.out = direct ? (void *)((char *)mapped + (int64_t)w.py * row_bytes) : (void *)(h->d_stage + whole_off[wi]);
+            a.y0 = w.ylocal;
+            a.out_h = w.npy;
+            const hipError_t e = golk::launch_view(a, h->stream);
+            if (e != hipSuccess) return fail(GOLHIP_EHIP, "view launch (strip %d): %s", i, hipGetErrorString(e));
+            ++wi;
+        }
+        if (int rc = view_span_end(h, e0, e1)) return rc;
+        h->view_frames++;
+        if (any_part && i != p.first) HIP_OR_FAIL(hipEventRecord(ev.part[i], h->stream));
+        if (!direct) {
+            wi = 0;
+            for (const ViewWhole &w : p.wholes) {
+                if (w.strip != i) continue;
+                HIP_OR_FAIL(hipMemcpyAsync((char *)out + (int64_t)w.py * row_bytes, h->d_stage + whole_off[wi],
+                                           (size_t)((int64_t)w.npy * row_bytes), hipMemcpyDeviceToHost, h->stream));
+                ++wi;
+            }
+        }
+    }
+    if (p.seams.empty()) return GOLHIP_OK;
+    // resolve on the first strip's stream, behind every other strip's count rows
+    golhip *h = res;
+    if (int rc = set_dev(h)) return rc;
+    std::vector<bool> waited(n, false);
+    for (const ViewPart &q : p.parts)
+        if (q.strip != p.first && !waited[q.strip]) {
+            HIP_OR_FAIL(hipStreamWaitEvent(h->stream, ev.part[q.strip], 0));
+            waited[q.strip] = true;
+        }
+    const bool direct = mapped && h->device == mapped_dev;
+    int64_t seam_off = 0;
+    for (const ViewWhole &w : p.wholes)
+        if (w.strip == p.first) seam_off += ((int64_t)w.npy * row_bytes + 15) / 16 * 16;
+    hipEvent_t e0, e1;
+    if (int rc = view_span_begin(h, &e0, &e1)) return rc;
+    for (size_t j0 = 0; j0 < p.seams.size(); j0 += golk::kViewResolveRows) {
+        golk::ViewResolveArgs r{};
+        r.counts = h->d_vcount;
+        r.cw = p.cw;
+        r.out_w = v->out_w;
+        r.s = v->scale;
+        r.format = v->format;
+        r.nrows = (int)std::min<size_t>(golk::kViewResolveRows, p.seams.size() - j0);
+        // staged: seam row j is row j of a frame of seam rows only
+        r.out = direct ? mapped : (void *)(h->d_stage + seam_off);
+        for (int j = 0; j < r.nrows; ++j) {
+            r.py[j] = direct ? p.seams[j0 + j].py : (int)(j0 + j);
+            r.slot[j] = p.seams[j0 + j].slot;
+            r.k[j] = p.seams[j0 + j].k;
+        }
+        const hipError_t e = golk::launch_view_resolve(r, h->stream);
+        if (e != hipSuccess) return fail(GOLHIP_EHIP, "view resolve launch: %s", hipGetErrorString(e));
+    }
+    if (int rc = view_span_end(h, e0, e1)) return rc;
+    HIP_OR_FAIL(hipEventRecord(ev.resolved, h->stream));
+    ev.resolved_set = true;
+    if (!direct)
+        for (size_t j = 0; j < p.seams.size(); ++j)
+            HIP_OR_FAIL(hipMemcpyAsync((char *)out + (int64_t)p.seams[j].py * row_bytes,
+                                       h->d_stage + seam_off + (int64_t)j * row_bytes, (size_t)row_bytes,
+                                       hipMemcpyDeviceToHost, h->stream));
+    return GOLHIP_OK;
+}
+
+int group_view_events(golhip_t *hs, int n, int first, GroupViewEvents *ev) {
+    ev->part.assign(n, nullptr);
+    for (int i = 0; i < n; ++i) {
+        HIP_OR_FAIL(hipSetDevice(hs[i]->device));
+        HIP_OR_FAIL(hipEventCreateWithFlags(&ev->part[i], hipEventDisableTiming));
+    }
+    HIP_OR_FAIL(hipSetDevice(hs[first]->device));
+    HIP_OR_FAIL(hipEventCreateWithFlags(&ev->resolved, hipEventDisableTiming));
+    return GOLHIP_OK;
+}
+
+// Synchronises every strip's stream, reports its flags, destroys the events.
+int group_view_finish(golhip_t *hs, int n, GroupViewEvents *ev, int rc) {
+    for (int i = 0; i < n; ++i) {
+        HIP_RC(hipSetDevice(hs[i]->device));
+        HIP_RC(hipStreamSynchronize(hs[i]->stream));
+        if (!rc) rc = take_skew_err(hs[i]);
+    }
+    for (hipEvent_t e : ev->part)
+        if (e) HIP_RC(hipEventDestroy(e));
+    if (ev->resolved) HIP_RC(hipEventDestroy(ev->resolved));
+    return rc;
+}
+}  // namespace
+
+extern "C" {
+
+int golhip_group_view_frame(golhip_t *hs, int32_t n, const golhip_view_t *v, void *out, uint64_t cap_bytes,
+                            int64_t *at_turn) {
+    bool torus = false;
+    if (int rc = group_view_check(hs, n, v, &torus)) return rc;
+    if (torus) return golhip_view_frame(hs[0], v, out, cap_bytes, at_turn);
+    if (!out) return fail(GOLHIP_EINVAL, "out is null");
+    GroupViewPlan p;
+    group_view_plan(hs, n, v, &p);
+    if (cap_bytes < p.bytes)
+        return fail(GOLHIP_ERANGE, "buffer holds %llu bytes, the frame needs %llu", (unsigned long long)cap_bytes,
+                    (unsigned long long)p.bytes);
+    std::vector<std::unique_lock<std::mutex>> locks;
+    for (int i = 0; i < n; ++i) locks.emplace_back(hs[i]->mu);
+    int mapped_dev = -1;
+    void *mapped = mapped_device_ptr(out, (size_t)p.bytes, &mapped_dev);
+    GroupViewEvents ev;
+    int rc = group_view_events(hs, n, p.first, &ev);
+    if (!rc) rc = group_view_enqueue(hs, n, v, p, ev, out, mapped, mapped_dev);
+    rc = group_view_finish(hs, n, &ev, rc);
+    if (!rc && at_turn) *at_turn = hs[0]->turns;
+    return rc;
+}
+
+int golhip_group_view_stream(golhip_t *hs, int32_t n, int64_t nturns, int64_t every, const golhip_view_t *v, void *out,
+                             uint64_t cap_frames, uint64_t *frames, int64_t *turns_done) {
+    if (frames) *frames = 0;
+    if (turns_done) *turns_done = 0;
+    bool torus = false;
+    if (int rc = group_view_check(hs, n, v, &torus)) return rc;
+    if (torus) return golhip_view_stream(hs[0], nturns, every, v, out, cap_frames, frames, turns_done);
+    if (nturns < 0) return fail(GOLHIP_EINVAL, "nturns %lld", (long long)nturns);
+    if (every < 1) return fail(GOLHIP_EINVAL, "every %lld", (long long)every);
+    GroupViewPlan p;
+    group_view_plan(hs, n, v, &p);
+    const uint64_t nf = (uint64_t)(nturns / every);
+    if (nf > cap_frames)
+        return fail(GOLHIP_ERANGE, "buffer holds %llu frames, %lld turns at every %lld need %llu",
+                    (unsigned long long)cap_frames, (long long)nturns, (long long)every, (unsigned long long)nf);
+    if (nf > 0 && !out) return fail(GOLHIP_EINVAL, "out is null");
+    std::vector<std::unique_lock<std::mutex>> locks;
+    for (int i = 0; i < n; ++i) locks.emplace_back(hs[i]->mu);
+    int mapped_dev = -1;
+    char *mapped = nf ? (char *)mapped_device_ptr(out, (size_t)(nf * p.bytes), &mapped_dev) : nullptr;
+    const int64_t turns0 = hs[0]->turns;
+    GroupViewEvents ev;
+    std::vector<hipEvent_t> ready(n, nullptr);  // group_step_locked's, kept over the whole run
+    int rc = group_view_events(hs, n, p.first, &ev);
+    for (int i = 0; i < n; ++i) {
+        HIP_RC(hipSetDevice(hs[i]->device));
+        HIP_RC(hipEventCreateWithFlags(&ready[i], hipEventDisableTiming));
+    }
+    for (uint64_t f = 0; f < nf && !rc; ++f) {
+        rc = group_step_locked(hs, n, every, 0, ready.data());
+        if (!rc)
+            rc = group_view_enqueue(hs, n, v, p, ev, (char *)out + f * p.bytes, mapped ? mapped + f * p.bytes : nullptr,
+                                    mapped_dev);
+    }
+    if (!rc) rc = group_step_locked(hs, n, nturns - (int64_t)nf * every, 0, ready.data());
+    rc = group_view_finish(hs, n, &ev, rc);
+    for (hipEvent_t e : ready)
+        if (e) HIP_RC(hipEventDestroy(e));
+    if (rc) return rc;
+    if (frames) *frames = nf;
+    if (turns_done) *turns_done = hs[0]->turns - turns0;
     return GOLHIP_OK;
 }
 

@@ -2,7 +2,7 @@
 // of gol.Run (gol_host.h) and libgolhip.so.
 //
 //   golrun [-t threads] [-w width] [-h height] [-turns n] [-noVis] [-root dir] [-device n]
-//          [-viewScale n] [-viewEvery n] [-viewDir dir]
+//          [-viewScale n] [-viewEvery n] [-viewDir dir] [-viewStrips]
 //
 // Same flags, defaults and output as main.go: "Threads: / Width: / Height:"
 // lines, then gol.Run on images/<w>x<h>.pgm with an events channel of
@@ -14,7 +14,9 @@
 // one GRAY8 pixel per n x n cells (width / n x height / n pixels), after every
 // -viewEvery-th turn (default 1) and writes every frame as
 // <viewDir>/view_<W>x<H>x<turn>.pgm (P5; -viewDir defaults to <root>/out/view):
-// the pixels a window would show (gol_host.h RunOptions::view).
+// the pixels a window would show (gol_host.h RunOptions::view).  On row strips
+// (GOL_STRIPS / GOL_NGPU) a view needs -viewStrips (or GOL_VIEW_STRIPS=1): the
+// frames are then rendered across the strips, the same pixels.
 // The headless drain loop ends at FinalTurnComplete (main.go:59-66) or when
 // the events channel closes.
 #include <sys/stat.h>
@@ -33,7 +35,7 @@ namespace {
 
 [[noreturn]] void usage(const char *msg) {
     std::fprintf(stderr, "golrun: %s\nusage: golrun [-t threads] [-w width] [-h height] [-turns n] [-noVis] "
-                         "[-root dir] [-device n] [-viewScale n] [-viewEvery n] [-viewDir dir]\n", msg);
+                         "[-root dir] [-device n] [-viewScale n] [-viewEvery n] [-viewDir dir] [-viewStrips]\n", msg);
     std::exit(2);
 }
 
@@ -90,6 +92,8 @@ int main(int argc, char **argv) {
             view_every = parse_int(value(), "viewEvery");
         } else if (key == "-viewDir") {
             view_dir = value();
+        } else if (key == "-viewStrips") {
+            opt.view_strips = (eq == std::string::npos || val == "true" || val == "1") ? 1 : 0;
         } else {
             usage(("flag provided but not defined: " + key).c_str());
         }

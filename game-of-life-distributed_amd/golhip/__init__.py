@@ -159,6 +159,9 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "golhip_board_hash": ([H, P(u64)], ctypes.c_int),
         "golhip_view_frame": ([H, P(View), ctypes.c_void_p, u64, P(i64)], ctypes.c_int),
         "golhip_view_stream": ([H, i64, i64, P(View), ctypes.c_void_p, u64, P(u64), P(i64)], ctypes.c_int),
+        "golhip_group_view_frame": ([P(H), i32, P(View), ctypes.c_void_p, u64, P(i64)], ctypes.c_int),
+        "golhip_group_view_stream": ([P(H), i32, i64, i64, P(View), ctypes.c_void_p, u64, P(u64), P(i64)],
+                                     ctypes.c_int),
         "golhip_perf": ([H, P(Perf)], ctypes.c_int),
         "golhip_perf_reset": ([H], ctypes.c_int),
         "golhip_persist_trace": ([H, P(u64)], ctypes.c_int),
@@ -513,6 +516,56 @@ def group_step(boards: list[Board], nturns: int, want_flips: bool = False) -> No
         _check(load().golhip_group_step(arr, len(boards), nturns))
 
 
+def _group_view(boards, x0, y0, scale, out_w, out_h, fmt) -> View:
+    """golhip_view_t of the strips' whole board; a missing out_w / out_h is the largest that fits."""
+    if not boards:
+        raise ValueError("no boards")
+    if out_w is None:
+        out_w = boards[0].width // max(scale, 1)
+    if out_h is None:
+        out_h = boards[0].height // max(scale, 1)
+    return View(x0, y0, scale, out_w, out_h, fmt)
+
+
+def group_view_frame(boards: list[Board], x0: int = 0, y0: int = 0, scale: int = 1, out_w: int | None = None,
+                     out_h: int | None = None, fmt: int = VIEW_ARGB, out: np.ndarray | None = None):
+    """golhip_group_view_frame: Board.view_frame of the whole board that the
+    strips `boards` (the group of group_step) hold: (frame, turn)."""
+    v = _group_view(boards, x0, y0, scale, out_w, out_h, fmt)
+    dt = np.dtype(np.uint8 if fmt == VIEW_GRAY8 else np.uint32)
+    n = max(v.out_w, 0) * max(v.out_h, 0)
+    if out is None:
+        out = np.empty(max(n, 1), dtype=dt)
+    if out.dtype != dt or out.size < n or not out.flags.c_contiguous:
+        raise ValueError(f"out must be a C-contiguous {dt} array of >= {n} pixels")
+    arr = (ctypes.c_void_p * len(boards))(*[b.handle for b in boards])
+    t = ctypes.c_int64()
+    _check(load().golhip_group_view_frame(arr, len(boards), ctypes.byref(v), _ptr(out), out.size * dt.itemsize,
+                                          ctypes.byref(t)))
+    return out.reshape(-1)[:n].reshape(v.out_h, v.out_w), t.value
+
+
+def group_view_stream(boards: list[Board], nturns: int, every: int, x0: int = 0, y0: int = 0, scale: int = 1,
+                      out_w: int | None = None, out_h: int | None = None, fmt: int = VIEW_ARGB,
+                      out: np.ndarray | None = None, cap_frames: int | None = None):
+    """golhip_group_view_stream: Board.view_stream on the strips `boards`:
+    (frames, turns_done), frames (n, out_h, out_w)."""
+    v = _group_view(boards, x0, y0, scale, out_w, out_h, fmt)
+    dt = np.dtype(np.uint8 if fmt == VIEW_GRAY8 else np.uint32)
+    n = max(v.out_w, 0) * max(v.out_h, 0)
+    if out is None:
+        cap = nturns // every if cap_frames is None and every > 0 else (cap_frames or 0)
+        out = np.empty(max(cap * n, 1), dtype=dt)
+    elif out.dtype != dt or not out.flags.c_contiguous:
+        raise ValueError(f"out must be a C-contiguous {dt} array")
+    cap = out.size // max(n, 1) if cap_frames is None else min(cap_frames, out.size // max(n, 1))
+    arr = (ctypes.c_void_p * len(boards))(*[b.handle for b in boards])
+    nf, done = ctypes.c_uint64(), ctypes.c_int64()
+    _check(load().golhip_group_view_stream(arr, len(boards), nturns, every, ctypes.byref(v), _ptr(out), cap,
+                                           ctypes.byref(nf), ctypes.byref(done)))
+    return out.reshape(-1)[: nf.value * n].reshape(nf.value, v.out_h, v.out_w), done.value
+
+
 def board_hash_np(words: np.ndarray, row0: int = 0) -> int:
     """Host restatement of golhip_board_hash for parity checks."""
     w = np.ascontiguousarray(words, dtype=np.uint32)
@@ -561,7 +614,7 @@ def view_frame_np(words: np.ndarray, width: int, height: int, x0: int = 0, y0: i
 # host mirror of gol.Run (libgolhost.so, include/golrun.h)
 # --------------------------------------------------------------------------
 HOST_LIB_PATH = os.environ.get("GOLHOST_LIB") or os.path.join(HERE, "libgolhost.so")  # A/B builds
-FLAG_KEYS, FLAG_REF_QUIRKS, FLAG_NO_CELL_EVENTS, FLAG_NO_TURN_EVENTS = 0x1, 0x2, 0x4, 0x8
+FLAG_KEYS, FLAG_REF_QUIRKS, FLAG_NO_CELL_EVENTS, FLAG_NO_TURN_EVENTS, FLAG_VIEW_STRIPS = 0x1, 0x2, 0x4, 0x8, 0x10
 ALIVE_CELLS_COUNT, IMAGE_OUTPUT_COMPLETE, STATE_CHANGE, CELL_FLIPPED, TURN_COMPLETE, FINAL_TURN_COMPLETE = range(6)
 PAUSED, EXECUTING, QUITTING = range(3)
 EVENT_NAMES = ["AliveCellsCount", "ImageOutputComplete", "StateChange", "CellFlipped", "TurnComplete",
@@ -624,8 +677,10 @@ class Run:
                  keys: bool = False, quirks: bool = False, cell_events: bool = True, turn_events: bool = True,
                  events_cap: int = 0, ticker_ms: int = 0, view: dict | None = None):
         """view: the live view (golrun_start_view), dict(scale=..., every=1,
-        x0=0, y0=0, out_w=None, out_h=None, fmt=VIEW_ARGB); missing out_w /
-        out_h are the largest that fit.  Run.view_frame() fetches frames."""
+        x0=0, y0=0, out_w=None, out_h=None, fmt=VIEW_ARGB, strips=False);
+        missing out_w / out_h are the largest that fit.  Run.view_frame()
+        fetches frames.  strips=True lets a run on row strips (GOL_STRIPS /
+        GOL_NGPU) render its view across them; without it such a run is refused."""
         lib = load_host()
         flags = (FLAG_KEYS if keys else 0) | (FLAG_REF_QUIRKS if quirks else 0) | \
             (0 if cell_events else FLAG_NO_CELL_EVENTS) | (0 if turn_events else FLAG_NO_TURN_EVENTS)
@@ -635,13 +690,15 @@ class Run:
             rc = lib.golrun_start(turns, threads, width, height, root.encode(), device, flags, events_cap, ticker_ms,
                                   ctypes.byref(h))
         else:
-            unknown = set(view) - {"scale", "every", "x0", "y0", "out_w", "out_h", "fmt"}
+            unknown = set(view) - {"scale", "every", "x0", "y0", "out_w", "out_h", "fmt", "strips"}
             if unknown or "scale" not in view:
                 raise ValueError(f"view needs scale; unknown keys {sorted(unknown)}")
             s = int(view["scale"])
             ow, oh = view.get("out_w"), view.get("out_h")
             self._view = View(view.get("x0", 0), view.get("y0", 0), s, width // max(s, 1) if ow is None else ow,
                               height // max(s, 1) if oh is None else oh, view.get("fmt", VIEW_ARGB))
+            if view.get("strips"):
+                flags |= FLAG_VIEW_STRIPS
             rc = lib.golrun_start_view(turns, threads, width, height, root.encode(), device, flags, events_cap,
                                        ticker_ms, ctypes.byref(self._view), int(view.get("every", 1)), ctypes.byref(h))
         if rc != 0:

@@ -368,6 +368,23 @@ int golhip_view_frame(golhip_t h, const golhip_view_t *v, void *out, uint64_t ca
  * frames exceed cap_frames.  Returns after the last frame has landed. */
 int golhip_view_stream(golhip_t h, int64_t nturns, int64_t every, const golhip_view_t *v, void *out,
                        uint64_t cap_frames, uint64_t *frames, int64_t *turns_done);
+/* The same frame of a board held as the n row strips hs (the group of
+ * golhip_group_step: one board, strips contiguous from row 0 and covering it,
+ * one word layout; all loaded and at the same turn, else GOLHIP_EINVAL).  v is
+ * a view of the whole torus: any viewport of at most one lap, across strip
+ * boundaries and both seams.  No strip's rows are copied: every strip renders
+ * the pixel rows that lie wholly inside it on its own stream and device, and
+ * for a pixel row that straddles strips each of them adds up its part of the
+ * alive counts, which the first strip of the viewport sums and normalises.
+ * With n == 1 and a whole-torus handle this is golhip_view_frame. */
+int golhip_group_view_frame(golhip_t *hs, int32_t n, const golhip_view_t *v, void *out, uint64_t cap_bytes,
+                            int64_t *at_turn);
+/* golhip_group_step(hs, n, every) with a group frame enqueued behind it,
+ * floor(nturns / every) times, with no host synchronisation between turns; then
+ * the remaining turns, and one synchronisation of every strip's stream.
+ * Results as golhip_view_stream (GOLHIP_ERANGE with nothing advanced). */
+int golhip_group_view_stream(golhip_t *hs, int32_t n, int64_t nturns, int64_t every, const golhip_view_t *v, void *out,
+                             uint64_t cap_frames, uint64_t *frames, int64_t *turns_done);
 
 /* ---- measurement ------------------------------------------------------ */
 int golhip_perf(golhip_t h, golhip_perf_t *out);

@@ -25,6 +25,8 @@ extern "C" {
                                             CellFlipped and s/q snapshots (DESIGN.md "Quirks") */
 #define GOLRUN_FLAG_NO_CELL_EVENTS 0x4u  /* no per-cell CellFlipped (fused turns, fast)     */
 #define GOLRUN_FLAG_NO_TURN_EVENTS 0x8u  /* no per-turn TurnComplete                        */
+#define GOLRUN_FLAG_VIEW_STRIPS 0x10u    /* golrun_start_view: a run on row strips renders its
+                                            view across them (golhip_group_view_frame)      */
 
 /* event kinds (gol/event.go) */
 #define GOLRUN_ALIVE_CELLS_COUNT 0
@@ -66,7 +68,9 @@ int golrun_start(int64_t turns, int64_t threads, int64_t width, int64_t height, 
  * event, the final board's before FinalTurnComplete.  With cell events on,
  * frames are rendered between the flip-stream batches instead (each shows its
  * batch's last turn).  Runs of more than one strip (GOL_STRIPS / GOL_NGPU)
- * are refused: golrun_wait reports the message. */
+ * are refused (golrun_wait reports the message) unless GOLRUN_FLAG_VIEW_STRIPS
+ * or the environment's GOL_VIEW_STRIPS=1 opts in: then the frames are
+ * golhip_group_view_frame's, the same pixels. */
 int golrun_start_view(int64_t turns, int64_t threads, int64_t width, int64_t height, const char *root,
                       int32_t device, uint32_t flags, int32_t events_cap, int32_t ticker_ms,
                       const golhip_view_t *view, int32_t every, golrun_t *out);

@@ -59,6 +59,14 @@ package gol
 //                                 uint64_t *frames, int64_t *done) {
 //     return gh_wrap(golhip_view_stream(h, t, every, v, out, cap, frames, done));
 // }
+// static gh_status gh_group_view_frame(golhip_t *hs, int32_t n, const golhip_view_t *v, void *out, uint64_t cap,
+//                                      int64_t *turn) {
+//     return gh_wrap(golhip_group_view_frame(hs, n, v, out, cap, turn));
+// }
+// static gh_status gh_group_view_stream(golhip_t *hs, int32_t n, int64_t t, int64_t every, const golhip_view_t *v,
+//                                       void *out, uint64_t cap, uint64_t *frames, int64_t *done) {
+//     return gh_wrap(golhip_group_view_stream(hs, n, t, every, v, out, cap, frames, done));
+// }
 import "C"
 
 import (
@@ -385,6 +393,29 @@ func (e *engine) ViewStream(n int, every int, v View) []uint32 {
 	var frames C.uint64_t
 	var done C.int64_t
 	check(C.gh_view_stream(e.hs[0], C.int64_t(n), C.int64_t(every), &cv, e.framesP,
+		C.uint64_t(len(e.frames)/(v.OutW*v.OutH)), &frames, &done))
+	return e.frames[:int(frames)*v.OutW*v.OutH]
+}
+
+// GroupViewFrame is ViewFrame on every strip of the engine
+// (golhip_group_view_frame): the viewport may cross strip boundaries and both
+// seams.  On one whole-torus handle it is ViewFrame.
+func (e *engine) GroupViewFrame(v View) ([]uint32, int) {
+	e.growFrames(v, 1)
+	cv := v.c()
+	var turn C.int64_t
+	check(C.gh_group_view_frame((*C.golhip_t)(unsafe.Pointer(&e.hs[0])), C.int32_t(len(e.hs)), &cv, e.framesP, C.uint64_t(len(e.frames)*4), &turn))
+	return e.frames[:v.OutW*v.OutH], int(turn)
+}
+
+// GroupViewStream is ViewStream on every strip of the engine
+// (golhip_group_view_stream).
+func (e *engine) GroupViewStream(n int, every int, v View) []uint32 {
+	e.growFrames(v, n/every)
+	cv := v.c()
+	var frames C.uint64_t
+	var done C.int64_t
+	check(C.gh_group_view_stream((*C.golhip_t)(unsafe.Pointer(&e.hs[0])), C.int32_t(len(e.hs)), C.int64_t(n), C.int64_t(every), &cv, e.framesP,
 		C.uint64_t(len(e.frames)/(v.OutW*v.OutH)), &frames, &done))
 	return e.frames[:int(frames)*v.OutW*v.OutH]
 }

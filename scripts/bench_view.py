@@ -1,6 +1,7 @@
 """The live view's cost (golhip_view_frame / golhip_view_stream).
 
     python scripts/bench_view.py [--out profiles/view/bench_view.json] [--quick]
+    python scripts/bench_view.py --strips 8 [--out profiles/view/bench_view_strips.json] [--quick]
 
 Timing follows bench.py: a warm-up call, then a host clock around calls that
 each end in a device synchronise, for at least a second per window.  Kernel
@@ -14,6 +15,13 @@ time is the library's own (GOLHIP_FLAG_TIMING events, perf view_kernel_ms).
 3. what showed a running board before: golhip_flip_stream (indices into
    page-locked memory) on 5120^2, and golhip_snapshot_bytes plus a numpy block
    sum for one look at 65536^2.
+--strips n measures only the view across row strips (golhip_group_view_frame)
+against the single-handle frame of the same run: the same board as one handle
+and as n strips on the same device, both into page-locked memory, timed
+alternately; once with the viewport at the origin (the H i / n strip
+boundaries of these boards fall on pixel rows: every pixel row lies in one
+strip) and once from row s / 2 (a pixel row straddles every boundary and the
+y seam: the counts + resolve path).
 Needs a GPU: without one it fails."""
 from __future__ import annotations
 
@@ -158,13 +166,83 @@ def parent_rows(quick):
     return out
 
 
+def strips_rows(nstrips, quick):
+    rows = []
+    cases = [(5120, 5, golhip.VIEW_GRAY8)]
+    if not quick:
+        cases.append((65536, 64, golhip.VIEW_ARGB))
+    for n, s, fmt in cases:
+        cuts = [n * i // nstrips for i in range(nstrips + 1)]
+        strips = []
+        with golhip.Board(n, n, timing=True) as one:
+            try:
+                for r0, r1 in zip(cuts, cuts[1:]):
+                    strips.append(golhip.Board(n, n, row0=r0, rows=r1 - r0, timing=True))
+                    strips[-1].fill_random(SEED)
+                one.fill_random(SEED)
+                one.step(3)
+                golhip.group_step(strips, 3)
+                ow = n // s
+                dt = np.uint8 if fmt == golhip.VIEW_GRAY8 else np.uint32
+                out_one, out_strips = golhip.host_array((ow * ow,), dt), golhip.host_array((ow * ow,), dt)
+                for y0 in (0, s // 2):
+                    def whole():
+                        one.view_frame(0, y0, s, fmt=fmt, out=out_one)
+
+                    def group():
+                        golhip.group_view_frame(strips, 0, y0, s, fmt=fmt, out=out_strips)
+
+                    whole()
+                    group()
+                    same = bool(np.array_equal(out_one, out_strips))
+                    for b in [one, *strips]:
+                        b.perf_reset()
+                    t_one, _ = timed(whole)
+                    t_grp, _ = timed(group)
+                    t_one2, _ = timed(whole)
+                    t_grp2, reps = timed(group)
+                    to, tg = min(t_one, t_one2), min(t_grp, t_grp2)
+                    p1, ps = one.perf(), [st.perf() for st in strips]
+                    rows.append({"board": f"{n}x{n}", "scale": s, "format": "GRAY8" if fmt else "ARGB8888",
+                                 "frame": f"{ow}x{ow}", "dest": "pinned", "strips": nstrips, "y0": y0,
+                                 "pixel_rows_across_strips": sum(1 for c in cuts[1:] if (c - y0) % s),
+                                 "equals_single_handle_frame": same,
+                                 "single_wall_us_per_frame": round(to * 1e6, 2),
+                                 "strips_wall_us_per_frame": round(tg * 1e6, 2), "strips_over_single": round(tg / to, 3),
+                                 "single_kernel_us_per_frame": round(p1["view_kernel_ms"] / p1["view_frames"] * 1e3, 2),
+                                 # the strips' kernels run side by side: their sum is device work, not elapsed time
+                                 "strips_kernel_us_per_frame_summed": round(
+                                     sum(p["view_kernel_ms"] for p in ps) / ps[0]["view_frames"] * 1e3, 2),
+                                 "strips_kernel_us_per_frame_slowest_strip": round(
+                                     max(p["view_kernel_ms"] / p["view_frames"] for p in ps) * 1e3, 2),
+                                 "frames_timed": reps})
+                    print(json.dumps(rows[-1]), flush=True)
+            finally:
+                for st in strips:
+                    st.close()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "view", "bench_view.json"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--quick", action="store_true", help="skip the 65536^2 boards")
+    ap.add_argument("--strips", type=int, default=0, help="only the view across this many row strips (>= 2)")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "view", "bench_view_strips.json" if a.strips else "bench_view.json")
     if golhip.device_count() < 1:
         raise SystemExit("bench_view: no HIP device")
+    if a.strips:
+        if a.strips < 2:
+            raise SystemExit("bench_view: --strips needs at least 2")
+        res = {"bench": "view_strips", "strips": a.strips, "frames": strips_rows(a.strips, a.quick)}
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+        print(json.dumps({"bench": "view_strips", "out": a.out}))
+        return
     link = golhip.host_link_probe(0, 64 << 20, 5)
     link_bps = link["kernel_write_GBps"] * 1e9
     res = {"bench": "view", "host_link_probe": link,
