@@ -830,54 +830,117 @@ struct PairSt {
     uint32_t c[D][WPL];
 };
 
-// One stage (turn t) of a row of phase PH (1: odd row, completes its pair).
-template <int D, int PH, int WPL>
-__device__ __forceinline__ void stage_pr(int t, Lanes<WPL> &x, PairSt<D, WPL> &st) {
-    uint32_t west[WPL], east[WPL];
-    if constexpr (WPL == 1) {
-        const uint32_t l = from_left_lane(x.w[0]);
-        const uint32_t r = from_right_lane(x.w[0]);
-        west[0] = __builtin_amdgcn_alignbit(x.w[0], l, 31);
-        east[0] = __builtin_amdgcn_alignbit(r, x.w[0], 1);
-    } else if constexpr (WPL == 4) {
-        const uint32_t l3 = from_left_lane(x.w[3]);
-        const uint32_t r0 = from_right_lane(x.w[0]);
-        west[0] = __builtin_amdgcn_alignbit(x.w[3], l3, 31);
-        west[1] = x.w[0];
-        west[2] = x.w[1];
-        west[3] = x.w[2];
-        east[0] = x.w[1];
-        east[1] = x.w[2];
-        east[2] = x.w[3];
-        east[3] = __builtin_amdgcn_alignbit(r0, x.w[0], 1);
-    } else {
-        const uint32_t l1 = from_left_lane(x.w[1]);
-        const uint32_t r0 = from_right_lane(x.w[0]);
-        west[0] = __builtin_amdgcn_alignbit(x.w[1], l1, 31);
-        east[0] = x.w[1];
-        west[1] = x.w[0];
-        east[1] = __builtin_amdgcn_alignbit(r0, x.w[0], 1);
-    }
-    uint32_t nx[WPL];
+// The lane shifts of a row: west of its first word and east of its last one
+// (the other words' neighbours are the lane's own words).  One DPP move and
+// one funnel shift each, all four half-rate: the spaced schedule below (unit_pr)
+// issues them one at a time, three LUTs or more apart.
+struct Shifted {
+    uint32_t w, e;
+};
+template <int WPL>
+__device__ __forceinline__ Shifted row_shifts(const Lanes<WPL> &x) {
+    const uint32_t l = from_left_lane(x.w[WPL - 1]);
+    const uint32_t r = from_right_lane(x.w[0]);
+    return {__builtin_amdgcn_alignbit(x.w[WPL - 1], l, 31), __builtin_amdgcn_alignbit(r, x.w[0], 1)};
+}
+// from_left_lane / from_right_lane for a source written at least three
+// instructions earlier (unit_pr: the row left its previous stage a unit ago,
+// or was moved in ahead of the unit's first LUTs).  As inline assembly: the
+// builtin ties an undefined `old` operand to the destination, and where the
+// register allocator reuses a register that a LUT has just written, the
+// compiler pads that false dependency with a 4-byte s_nop, which flips the
+// code parity of the rest of the group.  bound_ctrl writes
+// every lane, so there is no `old` to wait for.
+__device__ __forceinline__ uint32_t from_left_lane_far(uint32_t v) {
+    uint32_t r;
+    asm volatile("v_mov_b32_dpp %0, %1 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1" : "=v"(r) : "v"(v));
+    return r;
+}
+__device__ __forceinline__ uint32_t from_right_lane_far(uint32_t v) {
+    uint32_t r;
+    asm volatile("v_mov_b32_dpp %0, %1 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1" : "=v"(r) : "v"(v));
+    return r;
+}
+// vmov in a whole number of 8-byte slots together with the one s_waitcnt in
+// front of it (its first move in the 8-byte encoding), so that moving rows in
+// the middle of a group keeps the code after it on its parity.
+template <int WPL>
+__device__ __forceinline__ Lanes<WPL> vmov_even(const Lanes<WPL> &v) {
+    static_assert(WPL % 2 == 0, "s_waitcnt + one 8-byte move + an odd number of 4-byte ones");
+    Lanes<WPL> r;
+    asm volatile("v_mov_b32_e64 %0, %1" : "=v"(r.w[0]) : "v"(v.w[0]));
 #pragma unroll
-    for (int k = 0; k < WPL; ++k) {
-        const uint32_t n0 = bop<kXor3>(west[k], x.w[k], east[k]);
-        const uint32_t n1 = bop<kMaj>(west[k], x.w[k], east[k]);
-        if constexpr (PH == 1) {
-            uint32_t p0, p1, p2;
-            pair_sum(st.b0[t][k], st.b1[t][k], n0, n1, p0, p1, p2);
-            nx[k] = pair_rule(st.a0[t][k], st.a1[t][k], p0, p1, p2, st.c[t][k]);
-            st.p0[t][k] = p0;
-            st.p1[t][k] = p1;
-            st.p2[t][k] = p2;
-            st.a0[t][k] = n0;
-            st.a1[t][k] = n1;
-        } else {
-            nx[k] = pair_rule(n0, n1, st.p0[t][k], st.p1[t][k], st.p2[t][k], st.c[t][k]);
-            st.b0[t][k] = n0;
-            st.b1[t][k] = n1;
+    for (int k = 1; k < WPL; ++k) asm volatile("v_mov_b32 %0, %1" : "=v"(r.w[k]) : "v"(v.w[k]));
+    return r;
+}
+
+// One unit = one stage (turn t) of a row of phase PH (1: odd row, completes
+// its pair), software-pipelined: the row's own lane shifts `sh` were issued
+// during the unit before it, and this unit's LUTs carry the four shifts of the
+// next unit's row `xn` (-> shn).  The unit is a whole number of windows of
+// four 8-byte instructions (32 bytes of code), and a window holds at most one
+// shift, always as its last instruction: three LUTs and a shift, or four LUTs
+// (WPL 2: four windows with a shift for an even row, shift shift - shift
+// shift - for an odd one).  At that cadence the shifts' half rate hides
+// behind the instruction fetch and the stream issues like LUTs alone
+// (DESIGN.md §5.15).  Every shift sits between two sched barriers, so the
+// machine scheduler cannot move it out of its window.
+template <int D, int PH, int WPL>
+__device__ __forceinline__ void unit_pr(int t, Lanes<WPL> &x, const Shifted sh, PairSt<D, WPL> &st,
+                                        const Lanes<WPL> &xn, Shifted &shn) {
+    constexpr int OPS = PH == 1 ? 10 : 6;  // LUTs a word
+    constexpr int NL = OPS * WPL, NW = (NL + 4) / 4;
+    static_assert(NL % 4 == 0, "whole windows: 4 shifts + a multiple of 4 LUTs");
+    uint32_t l = 0, r = 0;
+    uint32_t n0[WPL], n1[WPL], u0[WPL], u1[WPL], u2[WPL], u3[WPL], s7[WPL], nx[WPL];
+    static_for<NL>([&](auto j_tag) {
+        constexpr int j = decltype(j_tag)::value, k = j / OPS, op = j % OPS;
+        if constexpr (op <= 1) {
+            uint32_t west, east;
+            if constexpr (k == 0) west = sh.w; else west = x.w[k - 1];
+            if constexpr (k == WPL - 1) east = sh.e; else east = x.w[k + 1];
+            if constexpr (op == 0) n0[k] = bop<kXor3>(west, x.w[k], east);
+            if constexpr (op == 1) n1[k] = bop<kMaj>(west, x.w[k], east);
+        } else if constexpr (PH == 1) {  // pair_sum: (u0, u1, u3) = b + n; pair_rule(a, that, c)
+            if constexpr (op == 2) u0[k] = bop<kXor2>(st.b0[t][k], n0[k], n0[k]);
+            if constexpr (op == 3) u2[k] = bop<kAnd2>(st.b0[t][k], n0[k], n0[k]);
+            if constexpr (op == 4) u1[k] = bop<kXor3>(st.b1[t][k], n1[k], u2[k]);
+            if constexpr (op == 5) u3[k] = bop<kMaj>(st.b1[t][k], n1[k], u2[k]);
+            if constexpr (op == 6) u2[k] = bop<kPrA>(st.a0[t][k], u0[k], st.c[t][k]);
+            if constexpr (op == 7) s7[k] = bop<kPrB>(st.a1[t][k], u1[k], u3[k]);
+            if constexpr (op == 8) u2[k] = bop<kPrC>(st.c[t][k], u2[k], s7[k]);
+            if constexpr (op == 9) {
+                nx[k] = bop<kPrNext>(u3[k], s7[k], u2[k]);
+                st.p0[t][k] = u0[k];
+                st.p1[t][k] = u1[k];
+                st.p2[t][k] = u3[k];
+                st.a0[t][k] = n0[k];
+                st.a1[t][k] = n1[k];
+            }
+        } else {  // pair_rule(n, p, c)
+            if constexpr (op == 2) u2[k] = bop<kPrA>(n0[k], st.p0[t][k], st.c[t][k]);
+            if constexpr (op == 3) s7[k] = bop<kPrB>(n1[k], st.p1[t][k], st.p2[t][k]);
+            if constexpr (op == 4) u2[k] = bop<kPrC>(st.c[t][k], u2[k], s7[k]);
+            if constexpr (op == 5) {
+                nx[k] = bop<kPrNext>(st.p2[t][k], s7[k], u2[k]);
+                st.b0[t][k] = n0[k];
+                st.b1[t][k] = n1[k];
+            }
         }
-    }
+        // shift i closes window i NW / 4 (the windows with a shift, spread
+        // evenly), after 4 LUT slots a window before it less the i shifts
+        static_for<4>([&](auto i_tag) {
+            constexpr int i = decltype(i_tag)::value;
+            if constexpr (j + 1 == 4 * (i * NW / 4) - i + 3) {
+                __builtin_amdgcn_sched_barrier(0);
+                if constexpr (i == 0) l = from_left_lane_far(xn.w[WPL - 1]);
+                if constexpr (i == 1) shn.w = __builtin_amdgcn_alignbit(xn.w[WPL - 1], l, 31);
+                if constexpr (i == 2) r = from_right_lane_far(xn.w[0]);
+                if constexpr (i == 3) shn.e = __builtin_amdgcn_alignbit(r, xn.w[0], 1);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        });
+    });
 #pragma unroll
     for (int k = 0; k < WPL; ++k) {
         st.c[t][k] = x.w[k];
@@ -885,35 +948,45 @@ __device__ __forceinline__ void stage_pr(int t, Lanes<WPL> &x, PairSt<D, WPL> &s
     }
 }
 
-// push_group on the pair state: rows of pushes KQ + 0, 1, 2 (mod 2).
-template <int D, int KQ, int WPL>
-__device__ __forceinline__ void push_group_pr(Lanes<WPL> &x0, Lanes<WPL> &x1, Lanes<WPL> &x2,
-                                              PairSt<D, WPL> &st) {
-    parity_fix<1>();
-    static_for<D + 2>([&](auto s_tag) {
-        constexpr int s = decltype(s_tag)::value;
-        parity_fix<2>();
-        if constexpr (s < D) stage_pr<D, (KQ + 0 + s) & 1, WPL>(s, x0, st);
-        if constexpr (s >= 1 && s - 1 < D) stage_pr<D, (KQ + 1 + s - 1) & 1, WPL>(s - 1, x1, st);
-        if constexpr (s >= 2) stage_pr<D, (KQ + 2 + s - 2) & 1, WPL>(s - 2, x2, st);
-    });
-}
-
-// push_group_pr for the last stages only (the drain): the group's rows enter
-// stage LO (push_group_hi on the pair state; the stages below LO are dead).
+// push_group on the pair state from stage LO on (LO > 0: the drain; the
+// stages below LO are dead): rows of pushes KQ + 0, 1, 2 (mod 2).  The units
+// run A(LO), then B(t), A(t + 1), C(t) for t = LO .. D - 1 (rows A, B, C =
+// x0, x1, x2): each unit's row left its previous stage at least two units
+// earlier, so its shifts can ride on the unit before it.  `sh` carries the
+// shifts of A(LO) in and those of the next group's first row out: that row,
+// `n0`, is moved into `xn` (waiting for its load) ahead of the last unit.
 template <int D, int KQ, int LO, int WPL>
 __device__ __forceinline__ void push_group_pr_hi(Lanes<WPL> &x0, Lanes<WPL> &x1, Lanes<WPL> &x2,
-                                                 PairSt<D, WPL> &st) {
+                                                 PairSt<D, WPL> &st, Shifted &sh, const Lanes<WPL> &n0,
+                                                 Lanes<WPL> &xn) {
     parity_fix<1>();
-    static_for<D + 2>([&](auto s_tag) {
-        constexpr int s = decltype(s_tag)::value;
-        if constexpr (s >= LO) {
-            parity_fix<2>();
-            if constexpr (s < D) stage_pr<D, (KQ + 0 + s) & 1, WPL>(s, x0, st);
-            if constexpr (s - 1 >= LO && s - 1 < D) stage_pr<D, (KQ + 1 + s - 1) & 1, WPL>(s - 1, x1, st);
-            if constexpr (s - 2 >= LO) stage_pr<D, (KQ + 2 + s - 2) & 1, WPL>(s - 2, x2, st);
+    Shifted nx;
+    unit_pr<D, (KQ + 0 + LO) & 1, WPL>(LO, x0, sh, st, x1, nx);
+    sh = nx;
+    static_for<D - LO>([&](auto t_tag) {
+        constexpr int t = LO + decltype(t_tag)::value;
+        parity_fix<2>();
+        if constexpr (t + 1 < D) {
+            unit_pr<D, (KQ + 1 + t) & 1, WPL>(t, x1, sh, st, x0, nx);
+            sh = nx;
+            unit_pr<D, (KQ + 0 + t + 1) & 1, WPL>(t + 1, x0, sh, st, x2, nx);
+            sh = nx;
+            unit_pr<D, (KQ + 2 + t) & 1, WPL>(t, x2, sh, st, x1, nx);
+            sh = nx;
+        } else {
+            unit_pr<D, (KQ + 1 + t) & 1, WPL>(t, x1, sh, st, x2, nx);
+            sh = nx;
+            xn = vmov_even(n0);
+            __builtin_amdgcn_sched_barrier(0);
+            unit_pr<D, (KQ + 2 + t) & 1, WPL>(t, x2, sh, st, xn, nx);
+            sh = nx;
         }
     });
+}
+template <int D, int KQ, int WPL>
+__device__ __forceinline__ void push_group_pr(Lanes<WPL> &x0, Lanes<WPL> &x1, Lanes<WPL> &x2, PairSt<D, WPL> &st,
+                                              Shifted &sh, const Lanes<WPL> &n0, Lanes<WPL> &xn) {
+    push_group_pr_hi<D, KQ, 0, WPL>(x0, x1, x2, st, sh, n0, xn);
 }
 
 // 9-LUT stage state (slots 1, 2 = pushes k - 2, k - 1 of a push k = 0 mod 3)
@@ -1098,6 +1171,7 @@ __device__ __forceinline__ uint32_t stream_skew(const StepArgs &a, int ab, int e
     for (int i = 0; i < WPL; ++i) q0.w[i] = q1.w[i] = q2.w[i] = 0u;
     int qoi = -8;  // the first body stores nothing real
     [[maybe_unused]] PairSt<D, WPL> st;  // PR: the main loop's and the drain's stage state
+    [[maybe_unused]] Shifted sh = {0u, 0u};  // PR: the lane shifts of the next group's first row
     // main: every stage on board rows (the bottom band of a stack to the end)
     const int kmain = S + (self ? 2 * D : 2 * SP::P(0));
     for (int i = 0; i < GOL_LOOP_PAD; ++i) asm volatile("s_nop 0");
@@ -1110,6 +1184,7 @@ __device__ __forceinline__ uint32_t stream_skew(const StepArgs &a, int ab, int e
         static_assert(KSTART % 6 == 0, "the pair main loop starts at an even push");
         {
             pr_enter<D, 0, WPL>(h0, h1, cc, st);
+            sh = row_shifts<WPL>(x0);  // the first unit's shifts; every later unit's ride on the unit before it
             for (; k < kmain; k += 6) {
                 {
                     const Lanes<WPL> n0 = load_next(), n1 = load_next(), n2 = load_next();
@@ -1118,14 +1193,17 @@ __device__ __forceinline__ uint32_t stream_skew(const StepArgs &a, int ab, int e
                     emit(q2, qoi + 2);
                     __builtin_amdgcn_sched_barrier(0);
                     Lanes<WPL> y0 = x0, y1 = x1, y2 = x2;
-                    push_group_pr<D, 0, WPL>(y0, y1, y2, st);
+                    Lanes<WPL> xn;
+                    push_group_pr<D, 0, WPL>(y0, y1, y2, st, sh, n0, xn);
                     q0 = y0;
                     q1 = y1;
                     q2 = y2;
                     qoi = k - 2 * D;
                     __builtin_amdgcn_sched_barrier(0);
-                    x0 = vmov(n0);
-                    x1 = vmov(n1);
+                    x0 = xn;  // moved within the group, ahead of its last unit
+                    // (full tiles: four bytes more between the groups, so the second
+                    // group's parity_fix needs one s_nop, not two)
+                    if constexpr (HALF) x1 = vmov(n1); else x1 = vmov_even(n1);
                     x2 = vmov(n2);
                 }
                 {
@@ -1135,13 +1213,14 @@ __device__ __forceinline__ uint32_t stream_skew(const StepArgs &a, int ab, int e
                     emit(q2, qoi + 2);
                     __builtin_amdgcn_sched_barrier(0);
                     Lanes<WPL> y0 = x0, y1 = x1, y2 = x2;
-                    push_group_pr<D, 1, WPL>(y0, y1, y2, st);
+                    Lanes<WPL> xn;
+                    push_group_pr<D, 1, WPL>(y0, y1, y2, st, sh, n0, xn);
                     q0 = y0;
                     q1 = y1;
                     q2 = y2;
                     qoi = k + 3 - 2 * D;
                     __builtin_amdgcn_sched_barrier(0);
-                    x0 = vmov(n0);
+                    x0 = xn;  // moved within the group, ahead of its last unit
                     x1 = vmov(n1);
                     x2 = vmov(n2);
                 }
@@ -1216,6 +1295,7 @@ __device__ __forceinline__ uint32_t stream_skew(const StepArgs &a, int ab, int e
             x0 = vmov(n0);  // waited here, not at the loop head (keeps parity_fix next to the group)
             x1 = vmov(n1);
             x2 = vmov(n2);
+            if constexpr (PR && D % 3 == 0) sh = row_shifts<WPL>(x0);  // the imported row replaces the prefetched one
         }
         // the pair rule: two groups a body (KQ 0, 1), as in the main loop; the
         // drain phases span multiples of 6 pushes when D = 0 mod 3 (2 P(j) with
@@ -1226,7 +1306,8 @@ __device__ __forceinline__ uint32_t stream_skew(const StepArgs &a, int ab, int e
             imports(k + 3, n0, n1, n2);
             __builtin_amdgcn_sched_barrier(0);
             Lanes<WPL> y0 = x0, y1 = x1, y2 = x2;
-            push_group_pr_hi<D, KQ, LO, WPL>(y0, y1, y2, st);
+            Lanes<WPL> xn;
+            push_group_pr_hi<D, KQ, LO, WPL>(y0, y1, y2, st, sh, n0, xn);
             parity_fix<1>();  // (the stores and LDS loads: most of a short phase's body)
             emit(q0, qoi);
             emit(q1, qoi + 1);
@@ -1236,7 +1317,7 @@ __device__ __forceinline__ uint32_t stream_skew(const StepArgs &a, int ab, int e
             q2 = y2;
             qoi = k - 2 * D;
             __builtin_amdgcn_sched_barrier(0);
-            x0 = vmov(n0);
+            x0 = xn;
             x1 = vmov(n1);
             x2 = vmov(n2);
             k += 3;

@@ -791,11 +791,15 @@ bool skew_plan(golhip_t h, int depth, int wpl, const golk::StepArgs &a, golk::Sk
     // half-wave-tile plans (16-turn launches of ramp-dominated bands): 60 %
     // (16384^2 87.6 vs 86.4 at 68, 83.7 at 55; profiles/r6b); whole tori on
     // full tiles 70 % (65536^2 128.7 vs 127.5-127.8 at 68, 126.4 at 74;
-    // profiles/r6i); ring strips 68 % (their sweep is within its noise, r6d)
+    // profiles/r6i); ring strips 68 % (their sweep is within its noise, r6d).
+    // The pair rule's spaced shifts leave the older wave's
+    // rate as it was and let the younger one issue in more of its gaps: whole
+    // tori on full tiles 80 % (65536^2 144.2 vs 136.8 at 70, 139.5 at 86);
+    // half tiles stay at 60 and ring strips at 68 (68-72 level; profiles/r8a)
     const int young = h->skew_young > 0 ? h->skew_young
                       : wpl == 4             ? 78
                       : sk->half             ? 60
-                      : a.in.wrap > 0        ? 70
+                      : a.in.wrap > 0        ? (sk->pairs ? 80 : 70)
                                              : 68;
     for (int q = 0; q < 8; ++q) sk->wgt[q] = (q < sy && q * sk->tx >= 4) ? young : 100;
     sk->prio_young = h->skew_prio;

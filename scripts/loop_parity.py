@@ -103,6 +103,39 @@ def inner_loops(lines, kernel, min_b8=300):
     raise KeyError(kernel)
 
 
+HALF_RATE = ("v_mov_b32_dpp", "v_alignbit_b32")
+
+
+def main_loop_mnemonics(lines, kernel):
+    """Mnemonics, in address order, of the kernel's main loop: its innermost
+    loop with the most 8-byte instructions."""
+    for name, body in kernels(lines):
+        if kernel not in name:
+            continue
+        ins, lps = loops(body)
+        inner = [l for l in lps if not any(o is not l and l[0] <= o[0] and o[1] <= l[1] and (o[1] - o[0]) >= 400
+                                           for o in lps)]
+        best = max(inner, key=lambda l: l[2]["b8@4"] + l[2]["b8@0"])
+        return [txt.split()[0] for x, _, txt in ins if best[0] <= x <= best[1]]
+    raise KeyError(kernel)
+
+
+def issue_classes(mnemonics):
+    """One letter per instruction: H = half-rate VALU (DPP move, funnel
+    shift), V = any other VALU, O = everything else."""
+    return "".join("H" if m.startswith(HALF_RATE) else "V" if m.startswith("v_") else "O" for m in mnemonics)
+
+
+def crowded_shifts(classes, gap):
+    """(half-rate instructions followed by another one within `gap`
+    instructions, all half-rate instructions) of a loop, around its back edge."""
+    pos = [i for i, c in enumerate(classes) if c == "H"]
+    if len(pos) < 2:
+        return 0, len(pos)
+    nxt = pos[1:] + [pos[0] + len(classes)]
+    return sum(1 for a, b in zip(pos, nxt) if b - a <= gap), len(pos)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("lib")

@@ -130,6 +130,45 @@ KERNEL(k_dpp2_alb2, P_dpp2_alb2)
 KERNEL(k_xor_e64, P_xor_e64)
 KERNEL(k_xor3, P_andor)
 
+// The pair rule at two words per lane: an even-row unit is 2 DPP + 2 alignbit
+// + 12 bitop3, an odd-row one 2 + 2 + 20 (8 : 1 : 1 over the two, 40
+// instructions).  Each alignbit reads its DPP move's result and the next
+// bitop3 reads the alignbit's.  pr_grouped: the order the compiler emitted
+// before the spaced schedule (DDAbA + 11 LUTs, DDAA + 20 LUTs); pr_gapK: one
+// shift after every K bitop3 (the bitop3 left over at the end); pr_gap3_5:
+// the spaced schedule's units (a shift after every 3 LUTs of an even-row
+// unit, after every 5 of an odd-row one).
+#define P_pr_grouped DPP(44,60) DPP(46,62) ALB(45,61,44) B3(40,45,49,50) ALB(47,63,46) B3(41,47,50,51) B3(42,50,51,52) B3(43,51,52,53) \
+    B3(40,52,53,54) B3(41,53,54,55) B3(42,54,55,56) B3(43,55,56,57) B3(40,56,57,58) B3(41,57,58,59) B3(42,58,59,60) B3(43,59,60,61) \
+    DPP(44,60) DPP(46,62) ALB(45,61,44) ALB(47,63,46) B3(40,47,49,50) B3(41,49,50,51) B3(42,50,51,52) B3(43,51,52,53) \
+    B3(40,52,53,54) B3(41,53,54,55) B3(42,54,55,56) B3(43,55,56,57) B3(40,56,57,58) B3(41,57,58,59) B3(42,58,59,60) B3(43,59,60,61) \
+    B3(40,48,49,50) B3(41,49,50,51) B3(42,50,51,52) B3(43,51,52,53) B3(40,52,53,54) B3(41,53,54,55) B3(42,54,55,56) B3(43,55,56,57)
+KERNEL(k_pr_grouped, P_pr_grouped)
+#define P_pr_gap2 B3(40,48,49,50) B3(41,49,50,51) DPP(44,60) B3(42,50,51,52) B3(43,51,52,53) ALB(45,61,44) B3(40,45,53,54) B3(41,53,54,55) \
+    DPP(46,62) B3(42,54,55,56) B3(43,55,56,57) ALB(47,63,46) B3(40,47,57,58) B3(41,57,58,59) DPP(44,60) B3(42,58,59,60) \
+    B3(43,59,60,61) ALB(45,61,44) B3(40,45,49,50) B3(41,49,50,51) DPP(46,62) B3(42,50,51,52) B3(43,51,52,53) ALB(47,63,46) \
+    B3(40,47,53,54) B3(41,53,54,55) B3(42,54,55,56) B3(43,55,56,57) B3(40,56,57,58) B3(41,57,58,59) B3(42,58,59,60) B3(43,59,60,61) \
+    B3(40,48,49,50) B3(41,49,50,51) B3(42,50,51,52) B3(43,51,52,53) B3(40,52,53,54) B3(41,53,54,55) B3(42,54,55,56) B3(43,55,56,57)
+KERNEL(k_pr_gap2, P_pr_gap2)
+#define P_pr_gap3 B3(40,48,49,50) B3(41,49,50,51) B3(42,50,51,52) DPP(44,60) B3(43,51,52,53) B3(40,52,53,54) B3(41,53,54,55) ALB(45,61,44) \
+    B3(42,45,55,56) B3(43,55,56,57) B3(40,56,57,58) DPP(46,62) B3(41,57,58,59) B3(42,58,59,60) B3(43,59,60,61) ALB(47,63,46) \
+    B3(40,47,49,50) B3(41,49,50,51) B3(42,50,51,52) DPP(44,60) B3(43,51,52,53) B3(40,52,53,54) B3(41,53,54,55) ALB(45,61,44) \
+    B3(42,45,55,56) B3(43,55,56,57) B3(40,56,57,58) DPP(46,62) B3(41,57,58,59) B3(42,58,59,60) B3(43,59,60,61) ALB(47,63,46) \
+    B3(40,47,49,50) B3(41,49,50,51) B3(42,50,51,52) B3(43,51,52,53) B3(40,52,53,54) B3(41,53,54,55) B3(42,54,55,56) B3(43,55,56,57)
+KERNEL(k_pr_gap3, P_pr_gap3)
+#define P_pr_gap4 B3(40,48,49,50) B3(41,49,50,51) B3(42,50,51,52) B3(43,51,52,53) DPP(44,60) B3(40,52,53,54) B3(41,53,54,55) B3(42,54,55,56) \
+    B3(43,55,56,57) ALB(45,61,44) B3(40,45,57,58) B3(41,57,58,59) B3(42,58,59,60) B3(43,59,60,61) DPP(46,62) B3(40,48,49,50) \
+    B3(41,49,50,51) B3(42,50,51,52) B3(43,51,52,53) ALB(47,63,46) B3(40,47,53,54) B3(41,53,54,55) B3(42,54,55,56) B3(43,55,56,57) \
+    DPP(44,60) B3(40,56,57,58) B3(41,57,58,59) B3(42,58,59,60) B3(43,59,60,61) ALB(45,61,44) B3(40,45,49,50) B3(41,49,50,51) \
+    B3(42,50,51,52) B3(43,51,52,53) DPP(46,62) B3(40,52,53,54) B3(41,53,54,55) B3(42,54,55,56) B3(43,55,56,57) ALB(47,63,46)
+KERNEL(k_pr_gap4, P_pr_gap4)
+#define P_pr_gap3_5 B3(40,48,49,50) B3(41,49,50,51) B3(42,50,51,52) DPP(44,60) B3(43,51,52,53) B3(40,52,53,54) B3(41,53,54,55) ALB(45,61,44) \
+    B3(42,45,55,56) B3(43,55,56,57) B3(40,56,57,58) DPP(46,62) B3(41,57,58,59) B3(42,58,59,60) B3(43,59,60,61) ALB(47,63,46) \
+    B3(40,47,49,50) B3(41,49,50,51) B3(42,50,51,52) B3(43,51,52,53) B3(40,52,53,54) DPP(44,60) B3(41,53,54,55) B3(42,54,55,56) \
+    B3(43,55,56,57) B3(40,56,57,58) B3(41,57,58,59) ALB(45,61,44) B3(42,45,59,60) B3(43,59,60,61) B3(40,48,49,50) B3(41,49,50,51) \
+    B3(42,50,51,52) DPP(46,62) B3(43,51,52,53) B3(40,52,53,54) B3(41,53,54,55) B3(42,54,55,56) B3(43,55,56,57) ALB(47,63,46)
+KERNEL(k_pr_gap3_5, P_pr_gap3_5)
+
 typedef void (*kfn)(int, long long*);
 
 int main(int argc, char** argv) {
@@ -143,7 +182,8 @@ int main(int argc, char** argv) {
     struct { const char* n; kfn f; int len; } ks[] = {{"indep", k_indep, k_indep_n}, {"bank3", k_bank3, k_bank3_n}, {"bank2", k_bank2, k_bank2_n},
         {"chain1", k_chain1, k_chain1_n}, {"chain2", k_chain2, k_chain2_n}, {"chain4", k_chain4, k_chain4_n}, {"dpp", k_dpp, k_dpp_n}, {"alignbit", k_alb, k_alb_n}, {"mix6:1:1", k_mix, k_mix_n}, {"mix9:1:1", k_mix911, k_mix911_n}, {"mix10:1:1", k_mix10, k_mix10_n},
         {"b3x15+dpp", k_d1, k_d1_n}, {"b3x15+alb", k_a1, k_a1_n}, {"b3x12+dpp4spread", k_d4s, k_d4s_n}, {"b3x12+alb4spread", k_a4s, k_a4s_n}, {"b3x12+dpp4grouped", k_d4g, k_d4g_n},
-        {"b3x12+alb4grouped", k_a4g, k_a4g_n}, {"xor_vop2", k_xor, k_xor_n}, {"real_HHHVVH", k_real_HHHVVH, k_real_HHHVVH_n}, {"real_spread", k_real_spread, k_real_spread_n}, {"HH_pairs", k_HH_pairs, k_HH_pairs_n}, {"HV_alt", k_HV_alt, k_HV_alt_n}, {"HVV", k_HVV, k_HVV_n}, {"HVVV", k_HVVV, k_HVVV_n}, {"bperm_alb", k_bperm_alb, k_bperm_alb_n}, {"bperm2_alb2", k_bperm2_alb2, k_bperm2_alb2_n}, {"dpp_alb", k_dpp_alb, k_dpp_alb_n}, {"dpp2_alb2", k_dpp2_alb2, k_dpp2_alb2_n}, {"xor_e64", k_xor_e64, k_xor_e64_n}, {"xor3", k_xor3, k_xor3_n}};
+        {"b3x12+alb4grouped", k_a4g, k_a4g_n}, {"xor_vop2", k_xor, k_xor_n}, {"real_HHHVVH", k_real_HHHVVH, k_real_HHHVVH_n}, {"real_spread", k_real_spread, k_real_spread_n}, {"HH_pairs", k_HH_pairs, k_HH_pairs_n}, {"HV_alt", k_HV_alt, k_HV_alt_n}, {"HVV", k_HVV, k_HVV_n}, {"HVVV", k_HVVV, k_HVVV_n}, {"bperm_alb", k_bperm_alb, k_bperm_alb_n}, {"bperm2_alb2", k_bperm2_alb2, k_bperm2_alb2_n}, {"dpp_alb", k_dpp_alb, k_dpp_alb_n}, {"dpp2_alb2", k_dpp2_alb2, k_dpp2_alb2_n}, {"xor_e64", k_xor_e64, k_xor_e64_n}, {"xor3", k_xor3, k_xor3_n},
+        {"pr_grouped", k_pr_grouped, k_pr_grouped_n}, {"pr_gap2", k_pr_gap2, k_pr_gap2_n}, {"pr_gap3", k_pr_gap3, k_pr_gap3_n}, {"pr_gap4", k_pr_gap4, k_pr_gap4_n}, {"pr_gap3_5", k_pr_gap3_5, k_pr_gap3_5_n}};
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));
