@@ -1,0 +1,471 @@
+// golhip_flips.cpp — flip lists: the three-pass compaction (golhip_flips,
+// golhip_alive_cells) and the flip stream (K5 per turn, K5r resident).
+#include "golhip_impl.h"
+#include <climits>
+#include <cstdlib>
+
+namespace gh GOLHIP_HIDDEN {
+
+// K5r (flip_overlap 2): copy blocks of the resident flip-stream launch
+static constexpr int kFlipStreamCopyBlocks = 128;
+static constexpr int64_t kFlipStreamMinBlocks = 64;  // (64 K words, e.g. 1448^2)
+
+int start_flips(golhip_t h) {
+    const int64_t nw = h->local_words();
+    const int64_t nb = golk::compact_blocks(nw);
+    int rc = h->d_blk.ensure(h, nb);
+    if (rc) return rc;
+    HIP_OR_FAIL(golk::launch_compact_count(h->cur_rows(), h->prev_rows(), nw, h->d_blk.p, h->stream));
+    HIP_OR_FAIL(golk::launch_compact_scan(h->d_blk.p, nb, h->d_scalars + 1, h->stream));
+    h->flips_valid = true;
+    h->flips_turn = h->turns;
+    return GOLHIP_OK;
+}
+
+// Room for n (x, y) pairs in d_xy (at least 4096).
+static int ensure_xy(golhip_t h, int64_t n) { return h->d_xy.ensure(h, 2 * n, false, 2 * 4096); }
+
+// Finish a compaction started with count+scan: read the total, scatter, copy out.
+static int finish_compact(golhip_t h, const uint32_t *a, const uint32_t *b, int32_t *xy, uint64_t cap, uint64_t *n) {
+    HIP_OR_FAIL(hipMemcpyAsync(h->h_scalars + 1, h->d_scalars + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                               h->stream));
+    if (int rc_ = sync_stream(h)) return rc_;
+    const uint64_t total = h->h_scalars[1];
+    if (n) *n = total;
+    if (total > cap || (!xy && total > 0))
+        return fail(GOLHIP_ERANGE, "buffer holds %llu cells, %llu needed", (unsigned long long)cap,
+                    (unsigned long long)total);
+    if (total == 0) return GOLHIP_OK;
+    int rc = ensure_xy(h, (int64_t)total);
+    if (rc) return rc;
+    HIP_OR_FAIL(golk::launch_compact_scatter(a, b, h->local_words(), h->Ww, h->row0, h->d_blk.p, h->d_xy.p, h->il, h->stream));
+    HIP_OR_FAIL(hipMemcpyAsync(xy, h->d_xy.p, total * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    if (int rc_ = sync_stream(h)) return rc_;
+    return GOLHIP_OK;
+}
+
+// One batch of the flip stream: the caller's request and what its paths share.
+struct FlipBatch {
+    int64_t nturns;
+    int format;
+    void *out;
+    uint64_t cap;
+    uint64_t *counts;
+    bool stop;
+    bool halo;       // the turns exchange a halo row first (golhip::halo_mode)
+    int esz;         // bytes an entry
+    int64_t nw;      // words of this handle's rows
+    uint64_t dcap;   // entries the lists can take: cap, or all a batch can ever hold
+    std::vector<unsigned long long> run;  // running list offsets, one more than turns
+    // K5 / K5r
+    void *direct;        // device address of `out` in golhip_host_alloc memory, or null
+    int64_t nb;          // compute blocks of a turn
+    int64_t nlaunch;     // turns launched
+    bool coresident;
+    golk::StepArgs sa;
+};
+
+// Generic widths (the 16 x 16 fixture) and giant strips: the three-pass
+// compaction one turn at a time, checked on the host after each turn.
+static int flip_generic(golhip_t h, FlipBatch &b, int64_t *done_out, uint64_t *total_out) {
+    const int64_t nw = b.nw, nturns = b.nturns;
+    const uint64_t dcap = b.dcap;
+    std::vector<unsigned long long> &run = b.run;
+    const int64_t nb = golk::compact_blocks(nw);
+    if (int rc = h->d_blk.ensure(h, nb)) return rc;
+    if (int rc = ensure_xy(h, (int64_t)std::min<uint64_t>(dcap, (uint64_t)nw * 32))) return rc;
+    if (int rc = set_layout(h, want_il(h))) return rc;
+    std::vector<int32_t> xy;
+    int64_t t = 0;
+    for (; t < nturns; ++t) {
+        if (b.halo)
+            if (int rc = exchange_rccl(h, 1, h->stream)) return rc;
+        if (int rc = launch_depth(h, 1, t == nturns - 1, b.halo)) return rc;
+        HIP_OR_FAIL(golk::launch_compact_count(h->cur_rows(), h->prev_rows(), nw, h->d_blk.p, h->stream));
+        HIP_OR_FAIL(golk::launch_compact_scan(h->d_blk.p, nb, h->d_scalars + 1, h->stream));
+        HIP_OR_FAIL(hipMemcpyAsync(h->h_scalars + 1, h->d_scalars + 1, 8, hipMemcpyDeviceToHost, h->stream));
+        if (int rc = sync_stream(h)) return rc;
+        const uint64_t k = h->h_scalars[1];
+        if (b.stop && run[t] + k > dcap) {  // roll back this turn
+            h->cur ^= 1;
+            h->turns -= 1;
+            h->alive_turn = -1;
+            run[t + 1] = run[t] + k;
+            break;
+        }
+        run[t + 1] = run[t] + k;
+        const uint64_t keep = run[t] >= dcap ? 0 : std::min<uint64_t>(k, dcap - run[t]);
+        if (keep > 0) {
+            HIP_OR_FAIL(golk::launch_compact_scatter(h->cur_rows(), h->prev_rows(), nw, h->Ww, h->row0, h->d_blk.p,
+                                                     h->d_xy.p, h->il, h->stream, (unsigned long long)(h->d_xy.cap / 2)));
+            xy.resize(2 * keep);
+            HIP_OR_FAIL(hipMemcpyAsync(xy.data(), h->d_xy.p, keep * 8, hipMemcpyDeviceToHost, h->stream));
+            if (int rc = sync_stream(h)) return rc;
+            for (uint64_t e = 0; e < keep; ++e) {
+                if (b.format == GOLHIP_FLIPS_XY) {
+                    static_cast<int32_t *>(b.out)[2 * (run[t] + e)] = xy[2 * e];
+                    static_cast<int32_t *>(b.out)[2 * (run[t] + e) + 1] = xy[2 * e + 1];
+                } else {
+                    static_cast<uint32_t *>(b.out)[run[t] + e] =
+                        (uint32_t)((uint64_t)xy[2 * e + 1] * (uint64_t)h->W + (uint64_t)xy[2 * e]);
+                }
+            }
+        }
+    }
+    const int64_t done = t;
+    for (int64_t i = 0; i < done; ++i) b.counts[i] = run[i + 1] - run[i];
+    *done_out = done;
+    *total_out = (b.stop && done < nturns) ? (done == 0 ? run[1] : run[done]) : run[done];
+    return GOLHIP_OK;
+}
+
+// The FlipTurnArgs fields every launch of a batch sets alike: those of a
+// copy-only launch, and (compute) those of a launch that also steps a turn.
+static golk::FlipTurnArgs flip_turn_args(golhip_t h, const FlipBatch &b, bool compute) {
+    golk::FlipTurnArgs a{};
+    a.Ww = h->Ww;
+    a.format = b.format == GOLHIP_FLIPS_XY ? golk::kFlipFormatXY : golk::kFlipFormatIdx;
+    a.cap = b.dcap;
+    a.ctl = h->d_ftctl.p;
+    a.stop_on_overflow = b.stop ? 1 : 0;
+    if (!compute) return a;
+    a.W = h->W;
+    a.rows = h->rows;
+    a.dst_base = kHalo;
+    a.in = b.sa.in;
+    a.row0 = h->row0;
+    a.ncompute = (int)b.nb;
+    a.status = h->d_ftstatus.p;
+    a.dbg = h->flip_debug;
+    return a;
+}
+
+// K5r: the whole batch in one launch (see FlipStreamArgs) whose `ncopy` copy
+// blocks move each turn's list to the host while the next turns compute.
+static int flip_resident_batch(golhip_t h, const FlipBatch &b, int ncopy, uint64_t board_bytes) {
+    const int64_t nlaunch = b.nlaunch;
+    // per turn kFtShards counters 128 B apart, then one turn count per compute block
+    const int64_t ndone = nlaunch * golk::kFtShards * golk::kFtShardStride + b.nb;
+    if (int rc = h->d_ftdone.ensure(h, ndone)) return rc;
+    HIP_OR_FAIL(hipMemsetAsync(h->d_ftdone.p, 0, (size_t)ndone * sizeof(unsigned), h->stream));
+    HIP_OR_FAIL(hipMemsetAsync(h->d_scalars, 0, sizeof(unsigned long long), h->stream));
+    golk::FlipStreamArgs fs{};
+    fs.turn = flip_turn_args(h, b, true);
+    fs.turn.out = h->d_ev.p;
+    fs.turn.coresident = 1;
+    fs.turn.board_bytes = (unsigned)board_bytes;
+    fs.turn.out_bytes = (unsigned)((uint64_t)b.dcap * b.esz);
+    fs.buf0 = h->buf[0];
+    fs.buf1 = h->buf[1];
+    fs.first = h->cur;
+    fs.nturns = (int)nlaunch;
+    // turn t's epoch is epoch0 + t: never 0 (the zeroed status words) in the batch
+    if (((h->flip_epoch + 1) & 0x3FFFFFu) + (unsigned)nlaunch > 0x3FFFFFu) h->flip_epoch = 0;
+    fs.epoch0 = (h->flip_epoch + 1) & 0x3FFFFFu;
+    h->flip_epoch = (fs.epoch0 + (unsigned)nlaunch - 1) & 0x3FFFFFu;
+    fs.run = h->d_run.p;
+    fs.done = h->d_ftdone.p;
+    fs.blk_done = h->d_ftdone.p + nlaunch * golk::kFtShards * golk::kFtShardStride;
+    fs.alive = h->d_scalars;
+    fs.cp_dst = b.direct;
+    fs.ncopy = ncopy;
+    fs.cp_groups = std::max(1, std::min(h->flip_cp_groups, ncopy / 8));
+    fs.timeout_ticks = 200000000ll;  // 2 s: only a block that never became resident waits that long
+    if (int rc = span_begin(h, h->stream)) return rc;
+    HIP_OR_FAIL(golk::launch_flip_stream(fs, h->stream));
+    if (int rc = span_end(h, 2)) return rc;
+    h->n.flip_launches += nlaunch;
+    h->n.flip_resident++;
+    h->cur ^= (int)(nlaunch & 1);
+    h->turns += nlaunch;
+    return GOLHIP_OK;
+}
+
+// One K5 launch per turn.  overlap (flip_overlap 1): each launch's `cpb` copy
+// blocks move the previous turn's list to the host, and a copy-only launch
+// the last turn's; else the turn's own blocks store into `out` (direct) or d_ev.
+static int flip_turn_loop(golhip_t h, const FlipBatch &b, bool overlap, int cpb) {
+    for (int64_t t = 0; t < b.nlaunch; ++t) {
+        if (b.halo)
+            if (int rc = exchange_rccl(h, 1, h->stream)) return rc;
+        const bool last = t == b.nlaunch - 1;
+        if (last) HIP_OR_FAIL(hipMemsetAsync(h->d_scalars, 0, sizeof(unsigned long long), h->stream));
+        golk::FlipTurnArgs a = flip_turn_args(h, b, true);
+        a.src = h->buf[h->cur];
+        a.dst = h->buf[h->cur ^ 1];
+        a.out = b.direct && !overlap ? b.direct : (void *)h->d_ev.p;
+        a.cp_run = overlap && t > 0 ? h->d_run.p + t - 1 : nullptr;
+        a.cp_dst = b.direct;
+        a.cp_blocks = cpb;
+        a.run = h->d_run.p + t;
+        a.ticket = h->d_ftticket.p + t;
+        h->flip_epoch = (h->flip_epoch + 1) & 0x3FFFFFu;
+        if (h->flip_epoch == 0) h->flip_epoch = 1;  // 0 is the zeroed status array's epoch
+        a.epoch = h->flip_epoch;
+        a.coresident = b.coresident ? 1 : 0;
+        a.alive = last ? h->d_scalars : nullptr;
+        if (int rc = span_begin(h, h->stream)) return rc;
+        HIP_OR_FAIL(golk::launch_flip_turn(a, h->stream));
+        if (int rc = span_end(h, 2)) return rc;
+        h->n.flip_launches++;
+        h->cur ^= 1;
+        h->turns += 1;
+    }
+    if (overlap && b.nlaunch > 0) {  // the last turn's list: a copy-only launch
+        golk::FlipTurnArgs a = flip_turn_args(h, b, false);
+        a.out = h->d_ev.p;
+        a.ncompute = 0;
+        a.cp_run = h->d_run.p + b.nlaunch - 1;
+        a.cp_dst = b.direct;
+        a.cp_blocks = 256;
+        if (int rc = span_begin(h, h->stream)) return rc;
+        HIP_OR_FAIL(golk::launch_flip_turn(a, h->stream));
+        if (int rc = span_end(h, 2)) return rc;
+    }
+    return GOLHIP_OK;
+}
+
+// The CellFlipped stream (distributor.go:93-173 with initializeAliveCells,
+// :212-220): up to nturns single turns, each with its flip list appended in
+// turn order to `out` (row-major within a turn; format: int32 (x, y) pairs or
+// uint32 y * W + x).  stop: never lose an entry — the batch ends before the
+// first turn whose list would not fit (the board is left at the last turn
+// that did, *done says which); otherwise the board advances nturns and the
+// lists are cut at cap (*total is what they needed).  counts[t] = entries
+// of turn t, for t < *done.
+static int flip_stream_locked(golhip_t h, int64_t nturns, int format, void *out, uint64_t cap, uint64_t *counts,
+                              int64_t *done_out, uint64_t *total_out, bool stop) {
+    *done_out = 0;
+    *total_out = 0;
+    if (!h->loaded) return fail(GOLHIP_EINVAL, "no board loaded");
+    if (h->nranks == 1 && !h->torus()) return fail(GOLHIP_EINVAL, "strip handle needs golhip_comm_init");
+    if (int rc = set_dev(h)) return rc;
+    h->flips_valid = false;
+    if (nturns == 0) return GOLHIP_OK;
+    FlipBatch b{};
+    b.nturns = nturns;
+    b.format = format;
+    b.out = out;
+    b.cap = cap;
+    b.counts = counts;
+    b.stop = stop;
+    b.halo = h->halo_mode();
+    const int esz = b.esz = format == GOLHIP_FLIPS_XY ? 8 : 4;
+    const int64_t nw = b.nw = h->local_words();
+    const uint64_t most = (uint64_t)nturns * (uint64_t)h->W * (uint64_t)h->rows;
+    const uint64_t dcap = b.dcap = std::min<uint64_t>({cap, most, (uint64_t)INT64_MAX / 16});
+    if (int rc = h->d_run.ensure(h, nturns + 1)) return rc;
+    b.run.assign((size_t)nturns + 1, 0);
+    std::vector<unsigned long long> &run = b.run;
+    unsigned ctl[2] = {0, 0};
+    const int64_t t0 = h->turns;
+    const int c0 = h->cur;
+
+    if (h->W % 32 != 0 || nw >= (1ll << 32) - 4096) return flip_generic(h, b, done_out, total_out);
+
+    // fused turn + list (K5) on the canonical layout; into a golhip_host_alloc
+    // buffer the entries go without a host-side copy (option "flip_overlap"):
+    //  2: K5r, the batch's turns in one resident launch whose copy blocks
+    //     move each turn's list to the host while the next turns compute
+    //     (round 6; where it cannot run: 1);
+    //  1: each K5 launch's copy blocks move the previous turn's list;
+    //  0: the turn's own blocks store their entries there directly
+    if (int rc = set_layout(h, 0)) return rc;
+    void *direct = b.direct = mapped_device_ptr(out, (size_t)dcap * esz);
+    const int64_t nb = b.nb = golk::flip_turn_blocks(nw);
+    const bool contig = h->Ww % 4 == 0;
+    const int bpc = std::min(golk::flip_turn_blocks_per_cu(contig), 4);
+    // every block resident at once (with a 10 % margin): block order = blockIdx.
+    // Not in a multi-rank ring: its fallback (restore, re-run in ticket order)
+    // would redo the batch's exchanges on this rank alone and hang the ring.
+    const bool coresident = b.coresident = !h->ft_ticket && !(h->ringed() && h->nranks > 1) && bpc > 0 &&
+                                           nb * 10 <= (int64_t)h->cu_count * bpc * 9;
+    // K5r: copy blocks in the slots the turn's blocks leave (up to 128), every
+    // block resident; whole tori (a strip exchanges halos between turns);
+    // buffers its 32-bit buffer offsets reach
+    const int ncopy_r = (int)std::min<int64_t>(kFlipStreamCopyBlocks, (int64_t)h->cu_count * std::max(bpc, 1) - nb);
+    const uint64_t board_bytes = (uint64_t)h->phys_rows * h->Ww * 4;
+    // (A/B of handles a caller creates itself, e.g. the gol.Run mirror's:
+    // GOLHIP_TUNING=1 GOLHIP_FLIP_OVERLAP=n overrides the option)
+    if (const char *e = getenv("GOLHIP_FLIP_OVERLAP"); e && tuning_env() && e[0] >= '0' && e[0] <= '3' && !e[1])
+        h->flip_overlap = e[0] - '0';
+    if (const char *e = getenv("GOLHIP_FLIP_CP_GROUPS"); e && tuning_env() && e[0] >= '1' && e[0] <= '8' && !e[1])
+        h->flip_cp_groups = e[0] - '0';
+    // (boards under kFlipStreamMinBlocks blocks keep per-turn launches: their
+    // lists are short, and K5r's per-turn waits cost more than a launch;
+    // configs[0] through gol.Run measured within noise, profiles/r7u)
+    const bool resident = direct && (h->flip_overlap == 3 || (h->flip_overlap == 2 && nb >= kFlipStreamMinBlocks)) &&
+                          coresident && !b.halo && ncopy_r >= 8 &&
+                          board_bytes < (1ull << 31) && (uint64_t)dcap * esz < (1ull << 31);
+    const int ov = !direct ? 0 : resident ? 2 : std::min(h->flip_overlap, 1);
+    const bool overlap = ov == 1;
+    // launch the turns the buffer probably holds (the last batch's largest
+    // list); turns past an overflow would only return at once
+    int64_t nlaunch = nturns;
+    if (stop && h->ft_est > 0) nlaunch = std::min<int64_t>(nturns, (int64_t)(dcap / h->ft_est) + 1);
+    b.nlaunch = nlaunch;
+    if (int rc = h->d_ftstatus.ensure(h, 3 * nb, true)) return rc;  // (K5r: three sets)
+    if (int rc = h->d_ftticket.ensure(h, nlaunch)) return rc;
+    if (int rc = h->d_ftctl.ensure(h, 2)) return rc;
+    if (!direct || ov)
+        if (int rc = h->d_ev.ensure(h, (int64_t)std::max<uint64_t>(dcap, 1) * esz)) return rc;
+    if (coresident) {  // keep the batch recoverable (see the error check below)
+        if (int rc = h->backup.ensure(h, h->local_words())) return rc;
+        HIP_OR_FAIL(hipMemcpyAsync(h->backup.p, h->cur_rows(), (size_t)h->local_words() * 4, hipMemcpyDeviceToDevice,
+                                   h->stream));
+    }
+    // every run bound zeroed: a turn that never ran (after a stop) reads as an
+    // empty list to the next launch's copy blocks
+    HIP_OR_FAIL(hipMemsetAsync(h->d_run.p, 0, (size_t)(nlaunch + 1) * sizeof(unsigned long long), h->stream));
+    // copy blocks: the slots the turn's blocks leave free (they come after
+    // them in the grid, so the turn's blocks stay co-resident), 32..256
+    const int cpb = overlap ? (int)std::max<int64_t>(32, std::min<int64_t>(256, (int64_t)h->cu_count * std::max(bpc, 1) - nb))
+                            : 0;
+    HIP_OR_FAIL(hipMemsetAsync(h->d_ftticket.p, 0, (size_t)nlaunch * sizeof(unsigned), h->stream));
+    HIP_OR_FAIL(hipMemsetAsync(h->d_ftctl.p, 0, 2 * sizeof(unsigned), h->stream));
+    b.sa = step_args(h, nullptr, b.halo);
+    if (ov == 2) {
+        if (nlaunch > 0)
+            if (int rc = flip_resident_batch(h, b, ncopy_r, board_bytes)) return rc;
+    } else if (int rc = flip_turn_loop(h, b, overlap, cpb)) {
+        return rc;
+    }
+    HIP_OR_FAIL(hipMemcpyAsync(run.data(), h->d_run.p, (size_t)(nlaunch + 1) * sizeof(unsigned long long),
+                               hipMemcpyDeviceToHost, h->stream));
+    HIP_OR_FAIL(hipMemcpyAsync(ctl, h->d_ftctl.p, sizeof ctl, hipMemcpyDeviceToHost, h->stream));
+    if (int rc = sync_stream(h)) return rc;
+    for (auto &r : run) r &= ~golk::kFtRunReady;  // (K5r's ready bit)
+    if (ctl[1]) {
+        if (!coresident) return fail(GOLHIP_EHIP, "flip stream: look-back spin bound exceeded (board undefined)");
+        // a block waited on a predecessor that never ran (a co-tenant kernel
+        // held CUs): restore the batch's first board, re-run it in ticket order
+        HIP_OR_FAIL(hipMemcpyAsync(h->buf[c0] + (int64_t)kHalo * h->Ww, h->backup.p, (size_t)h->local_words() * 4,
+                                   hipMemcpyDeviceToDevice, h->stream));
+        h->cur = c0;
+        h->turns = t0;
+        h->alive_turn = -1;
+        h->ft_ticket = true;
+        h->flip_fallbacks++;
+        h->flip_debug &= ~4;
+        return flip_stream_locked(h, nturns, format, out, cap, counts, done_out, total_out, stop);
+    }
+    int64_t done = nlaunch;
+    if (stop)
+        for (int64_t t = 0; t < nlaunch; ++t)
+            if (run[t + 1] > dcap) {
+                done = t;
+                break;
+            }
+    if (done < nlaunch) {  // turn `done` overflowed and the later launches returned at once
+        h->cur = (c0 + (int)(done & 1)) & 1;
+        h->turns = t0 + done;
+        h->alive_turn = -1;
+    } else {
+        h->alive_turn = h->turns;
+    }
+    uint64_t most_one = 0;
+    for (int64_t t = 0; t < done; ++t) {
+        counts[t] = run[t + 1] - run[t];
+        most_one = std::max<uint64_t>(most_one, counts[t]);
+    }
+    if (done > 0) h->ft_est = most_one;
+    const uint64_t total = done < nlaunch ? (done == 0 ? run[1] : run[done]) : run[nlaunch];
+    const uint64_t got = done == 0 && stop ? 0 : std::min<uint64_t>(run[done], cap);
+    if (got > 0 && !direct) {
+        HIP_OR_FAIL(hipMemcpyAsync(out, h->d_ev.p, got * esz, hipMemcpyDeviceToHost, h->stream));
+        if (int rc = sync_stream(h)) return rc;
+    }
+    h->n.flip_entries += (int64_t)got;
+    *done_out = done;
+    *total_out = total;
+    return GOLHIP_OK;
+}
+
+}  // namespace gh
+
+using namespace gh;
+
+extern "C" {
+
+int golhip_flips(golhip_t h, int32_t *xy, uint64_t cap, uint64_t *n) {
+    if (int rc = check(h)) return rc;
+    std::lock_guard<std::mutex> g(h->mu);
+    if (int rc = set_dev(h)) return rc;
+    if (!h->flips_valid || h->flips_turn != h->turns) {
+        if (n) *n = 0;
+        return fail(GOLHIP_EINVAL, "no flip list: step with want_flips first");
+    }
+    return finish_compact(h, h->cur_rows(), h->prev_rows(), xy, cap, n);
+}
+
+int golhip_step_flips(golhip_t h, int64_t nturns, int32_t *xy, uint64_t cap, uint64_t *counts, uint64_t *n) {
+    if (int rc = check(h)) return rc;
+    if (n) *n = 0;
+    if (nturns < 0) return fail(GOLHIP_EINVAL, "nturns %lld", (long long)nturns);
+    if (nturns > 0 && !counts) return fail(GOLHIP_EINVAL, "counts is null");
+    if (cap > 0 && !xy) return fail(GOLHIP_EINVAL, "xy is null");
+    std::lock_guard<std::mutex> g(h->mu);
+    // The flip kernel's look-back prefixes carry 40-bit offsets: run the batch
+    // in chunks whose lists cannot reach 2^40 entries (every cell flipping
+    // every turn), each appending after the last.
+    const uint64_t cells = std::max<uint64_t>(1, (uint64_t)h->W * (uint64_t)h->rows);
+    const int64_t chunk = std::max<int64_t>(1, (int64_t)((1ull << 40) / cells) - 1);
+    uint64_t total = 0;
+    for (int64_t t = 0; t < nturns || (t == 0 && nturns == 0);) {
+        const int64_t m = std::min<int64_t>(chunk, nturns - t);
+        const uint64_t got = std::min<uint64_t>(total, cap);
+        int64_t done = 0;
+        uint64_t part = 0;
+        if (int rc = flip_stream_locked(h, m, GOLHIP_FLIPS_XY, xy ? xy + 2 * got : nullptr, cap - got, counts + t, &done,
+                                        &part, false))
+            return rc;
+        total += part;
+        t += m;
+        if (m == 0) break;
+    }
+    if (n) *n = total;
+    if (total > cap)
+        return fail(GOLHIP_ERANGE, "buffer holds %llu cells, %llu needed", (unsigned long long)cap,
+                    (unsigned long long)total);
+    return GOLHIP_OK;
+}
+
+int golhip_flip_stream(golhip_t h, int64_t nturns, int32_t format, void *out, uint64_t cap, uint64_t *counts,
+                       int64_t *turns_done, uint64_t *n) {
+    if (int rc = check(h)) return rc;
+    if (n) *n = 0;
+    if (turns_done) *turns_done = 0;
+    if (nturns < 0) return fail(GOLHIP_EINVAL, "nturns %lld", (long long)nturns);
+    if (format != GOLHIP_FLIPS_XY && format != GOLHIP_FLIPS_INDEX) return fail(GOLHIP_EINVAL, "format %d", format);
+    if (nturns > 0 && (!counts || !turns_done || !n)) return fail(GOLHIP_EINVAL, "counts / turns_done / n is null");
+    if (cap > 0 && !out) return fail(GOLHIP_EINVAL, "out is null");
+    if (format == GOLHIP_FLIPS_INDEX && (uint64_t)h->W * (uint64_t)h->H > (1ull << 32))
+        return fail(GOLHIP_EINVAL, "cell indices of a %dx%d board do not fit in 32 bits", h->W, h->H);
+    std::lock_guard<std::mutex> g(h->mu);
+    if (h->ringed() && h->nranks > 1)
+        return fail(GOLHIP_EINVAL, "golhip_flip_stream stops early on one rank alone: use golhip_step_flips in a ring");
+    int64_t done = 0;
+    uint64_t total = 0;
+    if (int rc = flip_stream_locked(h, nturns, format, out, cap, counts, &done, &total, true)) return rc;
+    *turns_done = done;
+    *n = total;
+    if (nturns > 0 && done == 0)
+        return fail(GOLHIP_ERANGE, "buffer holds %llu entries, the next turn needs %llu", (unsigned long long)cap,
+                    (unsigned long long)total);
+    return GOLHIP_OK;
+}
+
+int golhip_alive_cells(golhip_t h, int32_t *xy, uint64_t cap, uint64_t *n) {
+    if (int rc = check(h)) return rc;
+    std::lock_guard<std::mutex> g(h->mu);
+    if (int rc = set_dev(h)) return rc;
+    const int64_t nw = h->local_words();
+    const int64_t nb = golk::compact_blocks(nw);
+    if (int rc = h->d_blk.ensure(h, nb)) return rc;
+    HIP_OR_FAIL(golk::launch_compact_count(h->cur_rows(), nullptr, nw, h->d_blk.p, h->stream));
+    HIP_OR_FAIL(golk::launch_compact_scan(h->d_blk.p, nb, h->d_scalars + 1, h->stream));
+    h->flips_valid = false;  // d_blk reused
+    return finish_compact(h, h->cur_rows(), nullptr, xy, cap, n);
+}
+
+}  // extern "C"

@@ -1,0 +1,327 @@
+// golhip_impl.h — what the host units of libgolhip.so share: the handle, the
+// error macros and the helpers that cross unit boundaries.  Host side only
+// (no kernel): owns the device boards, sequences the step kernels
+// (gol_kernels.hip) on one HIP stream, exchanges halo rows with the
+// neighbouring strips (RCCL ring or peer copies) and serves the side channels
+// (alive count, flip list, alive list, snapshots, frames).
+//
+// What each entry point replaces in the reference (gol/distributor.go):
+//   golhip_create / _load_bytes  world allocation + fill          :66-80
+//   golhip_step                  the turn loop                    :93-173
+//   golhip_flips                 initializeAliveCells             :212-220
+//   golhip_alive_count           len(calculateAliveCells) ticker  :283-302
+//   golhip_alive_cells           calculateAliveCells (final)      :180, :420-432
+//   golhip_snapshot_bytes        final/s/q raster streams         :186-191, :234-238
+//
+//   golhip_handle.cpp   handle lifetime, board I/O, counts, hash, perf, trace
+//   golhip_plan.cpp     launch planners (decisions on integers + occupancy caches)
+//   golhip_step.cpp     step launches, resident guard, RCCL ring, group step
+//   golhip_flips.cpp    flip lists and the flip stream (K5, K5r)
+//   golhip_view.cpp     live view of one handle and of a group of strips (K7)
+//   golhip_options.cpp  the option table and its consent rules
+//
+// Everything here but `struct golhip` lives in namespace gh, whose symbols
+// are hidden: libgolhip.so exports the C-ABI of include/golhip.h alone.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <rccl/rccl.h>
+
+#include <algorithm>
+#include <atomic>
+#include <cstdint>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+#include "../../include/golhip.h"
+#include "gol_kernels.h"
+
+// Internal linkage across units: nothing in namespace gh is a dynamic symbol.
+#define GOLHIP_HIDDEN __attribute__((visibility("hidden")))
+
+namespace gh GOLHIP_HIDDEN {
+
+using golk::kHalo;
+
+// Records the calling thread's last error (golhip_last_error) and returns `code`.
+int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+
+// Turns per launch with an instantiated step kernel (24: one word per lane
+// only, as 32; 9: four words per lane only, planned only under a cap of
+// exactly 9 (depth_cap); see max_depth_for).
+constexpr int kDepths[] = {32, 24, 20, 18, 16, 12, 9, 8, 6, 4, 2, 1};
+constexpr int kNumDepths = sizeof(kDepths) / sizeof(kDepths[0]);
+// trace buffer: 8 totals + (start, end) per (workgroup < 1024, wave < 64)
+constexpr int64_t kTraceWords = 8 + 2 * 1024 * 64;
+
+// Grow-only device scratch (contents are not kept): p holds cap elements.
+template <typename T>
+struct DevScratch {
+    T *p = nullptr;
+    int64_t cap = 0;
+    // Room for n elements, at least `floor` allocated; `zero`: cleared on h's stream when it grows.
+    int ensure(golhip *h, int64_t n, bool zero = false, int64_t floor = 1);
+    hipError_t release() {
+        const hipError_t e = hipFree(p);
+        if (e == hipSuccess) {
+            p = nullptr;
+            cap = 0;
+        }
+        return e;
+    }
+};
+
+// What golhip_perf reports and golhip_perf_reset zeroes: the integer counters
+// (a step that abandons a resident launch puts them back by copy) ...
+struct Counters {
+    int64_t step_launches = 0, step_turns = 0;
+    int64_t skew_launches = 0, skew_half_launches = 0, pair_launches = 0, pair_turns = 0;
+    int64_t persist_launches = 0, persist_turns = 0, lds_launches = 0;
+    int64_t halo_exchanges = 0, halo_bytes = 0;
+    int64_t flip_launches = 0, flip_entries = 0;
+    int64_t flip_resident = 0;  // K5r launches (flip_overlap 2)
+    int64_t view_frames = 0;    // frames rendered (K7)
+};
+// ... and the GOLHIP_FLAG_TIMING sums of the timed spans, by kind (drain_events)
+struct Millis {
+    double step = 0, persist = 0, flip = 0, halo = 0, view = 0;
+};
+
+}  // namespace gh
+
+#define HIP_OR_FAIL(expr)                                                                          \
+    do {                                                                                           \
+        hipError_t e_ = (expr);                                                                    \
+        if (e_ != hipSuccess) return gh::fail(GOLHIP_EHIP, "%s: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+
+// Accumulating form for loops that must finish their cleanup: sets `rc` once.
+#define HIP_RC(expr)                                                                            \
+    do {                                                                                        \
+        hipError_t e_ = (expr);                                                                 \
+        if (e_ != hipSuccess && rc == GOLHIP_OK)                                                \
+            rc = gh::fail(GOLHIP_EHIP, "%s: %s", #expr, hipGetErrorString(e_));                 \
+    } while (0)
+
+#define NCCL_OR_FAIL(expr)                                                                              \
+    do {                                                                                                \
+        ncclResult_t r_ = (expr);                                                                       \
+        if (r_ != ncclSuccess) return gh::fail(GOLHIP_ERCCL, "%s: %s", #expr, ncclGetErrorString(r_)); \
+    } while (0)
+
+struct golhip {
+    int W = 0, H = 0, Ww = 0;
+    int row0 = 0, rows = 0;  // this handle's rows of the torus
+    bool strip = false;      // created by golhip_create_strip
+    int device = 0;
+    uint32_t flags = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+
+    uint32_t *buf[2] = {nullptr, nullptr};
+    int cur = 0;
+    int64_t phys_rows = 0;
+
+    int tb_depth = 20;          // per-launch WPL-2 kernels fuse up to 20, the resident kernel 16
+    int rows_per_wave = 0;      // 0 = automatic (per depth, from occupancy)
+    int cu_count = 0;           // CUs the launches are planned for (option "cu_count": fewer)
+    int dev_cu = 0;             // the device's CUs
+    int fill_skip = 1;          // option "fill_skip"
+    int last_variant = 1;           // kernel family of the last step launch (golhip_perf kernel_variant)
+    int skew = 1;                   // option "skew": skewed band stacks (K1w) for per-launch steps
+    int skew_young = 0;             // option "skew_young": band height of waves 4..7, % of waves 0..3's (0: by kernel)
+    int skew_hcap = -1;             // option "skew_hcap": rows a stack's bottom band gives up (-1: 3 D / 4)
+    int skew_prio = 0;              // option "skew_prio": s_setprio 1 for waves 4..7
+    int skew_tx = 0;                // option "skew_tx": tiles per K1w workgroup (0: plan, 1 or 2)
+    int skew_half = 0;              // option "skew_half": half-wave tiles (0: when fewer wave-rows, 1: whenever possible, -1: never)
+    int lds_bpc[4] = {};               // K1r workgroups per CU by (wpl, 512 / 1024 threads) at lds_bpc_bytes of LDS
+    int64_t lds_bpc_bytes[4] = {};
+    int lds_bpc_stride[4] = {};
+    int skew_bpc[gh::kNumDepths][12] = {};  // K1w workgroups per CU by (depth, wpl, half, pairs) (0: not queried)
+    int skew_pairs = 5;             // option "skew_pairs": the pair rule (8 LUTs a word-turn) at depth 18 (depth_cap)
+    unsigned *skew_err = nullptr;      // host-mapped spin-bound flag of the K1w kernels
+    unsigned *skew_err_dev = nullptr;
+    int lds_band = -1;              // option "lds_band": resident LDS bands K1r (1 on where it fits, 0 off, -1 auto)
+    int lds_depth = 0;              // option "lds_depth": turns per K1r super-step (0: plan)
+    int lds_xcd = 1;                // option "lds_xcd": consecutive K1r bands on one XCD
+    int lds_waves = 0;              // option "lds_waves": K1r waves per workgroup (8 or 16; 0: plan)
+    int lds_wg_cu = 1;              // option "lds_wg_cu": K1r bands (workgroups) per CU (1 or 2)
+    int lds_stride = 1;             // option "lds_stride": K1r LDS rows at a compile-time stride where instantiated
+    int resident_fault = 0;         // option "resident_fault" (tests): K1r band 0 / K1p workgroup 0 never report
+                                    // (their neighbours' bounded waits time out: the restore-and-re-run path)
+    int lds_age = 0;                // option "lds_age": K1r run rows of a younger wave rank, % of the older's (0: plan)
+    int lds_pre = 2;                // option "lds_pre": K1r interior-first turns while the halos travel
+                                    // (profiles/r4pre: 8192^2 31.4 -> 33.9 TCUPS at 2; 1: 33.2, 3: 33.1, 4: 32.3)
+    gh::DevScratch<uint32_t> lds_edge;  // K1r edge rows (golk::lds_band_edge_words)
+    int persistent = -1;        // option "persistent": K1p for long torus runs (1 on, 0 off, -1 auto)
+    int wpl_opt = 0;            // option "wpl": words per lane (0 = auto, 1, 2, 4)
+    int persist_depth = 0;      // option "persist_depth" (0: tb_depth)
+    int persist_waves = 0;      // option "persist_waves": waves per workgroup (0: default)
+    int paired_bands = 1;       // option "paired_bands": SIMD mates share two bands from both ends (persistent)
+    int dummy_rows = 0;         // option "dummy_rows": halo rows taking the kernels' dummy stores (0: all)
+    int persist_wg_tx = 0;      // option "persist_wg_tx": tiles across a persistent workgroup (0: plan)
+    int persist_half = 1;       // option "persist_half": a D/2-turn remainder runs as the resident kernel's last super-step
+    unsigned long long *d_trace = nullptr;  // option "trace": persistent-kernel diagnostics
+    unsigned *d_sync = nullptr; // persistent kernel: [0] error, [1..] progress per workgroup
+    unsigned *h_err = nullptr;  // pinned copy of the error word
+    bool persist_pending = false;
+    // resident-launch guard (torus): the board as it was before the step's
+    // resident launch, restored and re-run on the per-launch kernels if that
+    // launch times out (its workgroups were not all co-resident)
+    gh::DevScratch<uint32_t> backup;
+    bool guarded = false;
+    bool guard_light = false;  // the guarded step is one source-keeping launch: its source is the copy
+    // the error word d_sync[0] is sticky over a guarded step: only its first
+    // resident launch clears it, so a later launch (steps past resident_max
+    // turns, a one-rank ring's rounds) can neither wipe an earlier timeout nor
+    // run on a drained board unnoticed (its waits see the word and drain too)
+    bool err_clear = true;
+    int resident_max = (int)golk::kResidentMaxTurns;  // turns a resident launch takes (test hook "resident_max_turns")
+    int64_t persist_fallbacks = 0;
+    int64_t persist_timeout_ticks = 100000000ll;  // 1 s at the 100 MHz s_memrealtime clock (option "persist_timeout_us")
+    int auto_rpw[gh::kNumDepths] = {};  // cache per depth index
+    bool loaded = false;
+    int il = 0;                 // word layout of the board: 0 canonical, 2 interleaved pairs, 4 quads (= wpl)
+    std::atomic<int64_t> turns{0};
+
+    // side-channel scratch
+    unsigned long long *d_scalars = nullptr;  // [0] alive, [1] compaction total, [2] hash
+    unsigned long long *h_scalars = nullptr;  // pinned mirror
+    int64_t alive_turn = -1;                  // turn whose count sits in d_scalars[0]
+    gh::DevScratch<unsigned long long> d_blk;
+    gh::DevScratch<int32_t> d_xy;             // (x, y) pairs: two elements a cell
+    gh::DevScratch<unsigned long long> d_run;  // flip streams: running list offsets
+    // flip stream (K5, golhip_flip_stream / golhip_step_flips)
+    gh::DevScratch<unsigned long long> d_ftstatus;  // look-back word per block (zeroed once)
+    gh::DevScratch<unsigned> d_ftticket;            // virtual block ids, one counter per turn
+    gh::DevScratch<unsigned> d_ftctl;               // [0] stop, [1] look-back spin error
+    gh::DevScratch<unsigned char> d_ev;             // entries of a batch
+    unsigned flip_epoch = 0;
+    int flip_debug = 0;  // option "flip_debug" (measurement only: wrong lists)
+    int flip_cp_groups = 4;  // K5r copy-block groups (GOLHIP_TUNING=1 GOLHIP_FLIP_CP_GROUPS=n, 1..8)
+    int flip_overlap = 2;  // option "flip_overlap": how lists reach golhip_host_alloc memory (flip_batch)
+    gh::DevScratch<unsigned> d_ftdone;  // K5r: kFtShards done counters a turn
+    bool ft_ticket = false;       // K5 block order by ticket (set after a co-residency failure)
+    uint64_t ft_est = 0;          // most entries of one turn in the last batch (launch sizing)
+    int64_t flip_fallbacks = 0;
+    gh::DevScratch<uint8_t> d_stage;    // byte staging for load/snapshot
+    gh::DevScratch<uint32_t> d_vcount;  // group view: count rows of the pixel rows that straddle strips
+    bool flips_valid = false;
+    int64_t flips_turn = -1;
+
+    // ring
+    ncclComm_t comm = nullptr;
+    // test hook (golhip_test_ring_init): a ring whose halo exchange runs
+    // through a host callback instead of RCCL (two processes on one device)
+    golhip_test_transport_fn xport = nullptr;
+    void *xport_user = nullptr;
+    uint32_t *xport_host = nullptr;  // pinned: send up, send down, recv top, recv bottom
+    int64_t xport_cap = 0;           // words per block
+    bool ringed() const { return comm || xport; }
+    int force_halo = 0;         // option "force_halo": one-rank RCCL ring on a whole board (tests)
+    int nranks = 1, rank = 0;
+    int ring_rows = 0;          // smallest strip of the ring (every rank plans from it)
+    int halo_skip = 0;          // option "halo_skip" (measurement only: no exchange, wrong halos)
+    // halo mode: row strips of a multi-rank ring, or (option force_halo) a
+    // whole board run as a one-rank RCCL ring
+    bool halo_mode() const { return ringed() && (nranks > 1 || force_halo); }
+
+    // measurement
+    std::vector<hipEvent_t> ev_pool;
+    struct Timed {
+        hipEvent_t e0, e1;
+        int kind;  // 0 per-launch step, 1 resident step, 2 flip turn (K5), 3 halo exchange, 4 view frame (K7)
+    };
+    std::vector<Timed> ev_pending;
+    hipEvent_t span_e0 = nullptr, span_e1 = nullptr;  // the open timed span (span_begin) ...
+    hipStream_t span_stream = nullptr;                // ... and the stream it is recorded on
+    gh::Counters n;
+    gh::Millis ms;  // (halo: exchange time on the engine stream)
+
+    std::mutex mu;
+
+    int64_t local_words() const { return (int64_t)rows * Ww; }
+    uint32_t *cur_rows() const { return buf[cur] + (int64_t)golk::kHalo * Ww; }
+    uint32_t *prev_rows() const { return buf[cur ^ 1] + (int64_t)golk::kHalo * Ww; }
+    bool torus() const { return nranks == 1 && rows == H; }
+};
+
+namespace gh GOLHIP_HIDDEN {
+
+template <typename T>
+int DevScratch<T>::ensure(golhip *h, int64_t n, bool zero, int64_t floor) {
+    if (cap >= n) return GOLHIP_OK;
+    if (p) HIP_OR_FAIL(hipFree(p));
+    p = nullptr;
+    cap = 0;
+    const int64_t want = std::max(n, floor);
+    if (hipError_t e = hipMalloc((void **)&p, (size_t)want * sizeof(T)); e != hipSuccess) {
+        p = nullptr;
+        return fail(GOLHIP_EHIP, "hipMalloc(%lld x %zu bytes): %s", (long long)want, sizeof(T), hipGetErrorString(e));
+    }
+    if (zero) HIP_OR_FAIL(hipMemsetAsync(p, 0, (size_t)want * sizeof(T), h->stream));
+    cap = want;
+    return GOLHIP_OK;
+}
+
+// ---- golhip_handle.cpp ----------------------------------------------------
+int check(golhip_t h);    // a non-null handle
+int set_dev(golhip_t h);  // hipSetDevice(h->device)
+// Device address of [p, p + bytes) if it lies inside one golhip_host_alloc buffer.
+void *mapped_device_ptr(const void *p, size_t bytes, int *device = nullptr);
+// A timed span of work on stream `st`: two events around it, their time added
+// to the sum of `kind` (golhip::Timed) at the next drain.  Nothing is
+// recorded without GOLHIP_FLAG_TIMING.  One span at a time per handle.
+// drain: the pending spans are summed here once 4096 have gathered (this
+// synchronises on their events; per-launch steps and view frames, whose count
+// a caller's golhip_perf calls do not bound).
+int span_begin(golhip_t h, hipStream_t st);
+int span_end(golhip_t h, int kind, bool drain = false);
+int drain_events(golhip_t h);
+int take_skew_err(golhip_t h);
+int sync_stream(golhip_t h);  // synchronise, then take_skew_err and the resident launch's flag
+int set_layout(golhip_t h, int il);
+
+// ---- golhip_plan.cpp --------------------------------------------------------
+struct DepthRun {
+    int d;
+    int64_t n;
+};
+struct HaloRun {
+    int d, k;
+};
+int largest_depth(int64_t want);
+DepthRun depth_plan(int cap, int64_t left);
+int sched_rows(golhip_t h);
+int persist_nw_for(golhip_t h, int depth, int wpl);
+bool persist_on(golhip_t h);
+int wpl_for(golhip_t h);
+int want_il(golhip_t h);
+int depth_cap(golhip_t h, bool halo);
+int next_depth(golhip_t h, int64_t remaining, bool halo);
+bool tb_paired(golhip_t h);
+int rows_per_wave_for(golhip_t h, int depth);
+void halo_plan(int strip_rows, int nranks, int rank, int depth, int Ww, golhip_halo_plan_t *p);
+bool skew_dims(golhip_t h, int depth, int wpl, int L, golk::SkewArgs *sk);
+bool skew_plan(golhip_t h, int depth, int wpl, const golk::StepArgs &a, golk::SkewArgs *sk);
+int halo_launches(int rows, int depth, int64_t run);
+HaloRun halo_next(int cap, int rows, bool resident, int64_t left);
+bool lds_fits(golhip_t h, int wpl, golk::LdsBandArgs *out = nullptr);
+int persist_depth_for(golhip_t h, int wpl);
+
+// ---- golhip_step.cpp --------------------------------------------------------
+golk::StepArgs step_args(golhip_t h, unsigned long long *alive, bool halo);
+int exchange_rccl(golhip_t h, int depth, hipStream_t st);
+int launch_depth(golhip_t h, int depth, bool count, bool halo);
+int step_checked_locked(golhip_t h, int64_t nturns, int32_t want_flips);
+int group_check(golhip_t *hs, int32_t n);
+int group_step_locked(golhip_t *hs, int32_t n, int64_t nturns, int32_t want_flips, hipEvent_t *keep = nullptr);
+
+// ---- golhip_flips.cpp -------------------------------------------------------
+int start_flips(golhip_t h);
+
+// ---- golhip_options.cpp -----------------------------------------------------
+bool tuning_env();      // GOLHIP_TUNING=1 (or GOLHIP_MEASUREMENT=1)
+bool test_hooks_env();  // GOLHIP_TEST_HOOKS=1
+
+}  // namespace gh

@@ -88,7 +88,7 @@ def test_halo_schedule(rows, tb, left, want):
     (16384, 16, 36, [(12, 3)]),
 ])
 def test_halo_schedule_sequence(rows, tb, left, want):
-    """The whole schedule (golhip.hip depth_plan): fewest launches, then the
+    """The whole schedule (golhip_plan.cpp depth_plan): fewest launches, then the
     largest smallest launch, in descending depth order."""
     seq, l = [], left
     while l > 0:
@@ -154,7 +154,7 @@ def test_wrong_result_macro_is_a_compile_error(tmp_path):
 def test_resident_turn_bound(tmp_path):
     """K1r's / K1p's super-step arithmetic is 32-bit.  A step of
     more than golk::kResidentMaxTurns turns runs as several resident launches
-    of at most that many (golhip.hip step_locked), and at that bound
+    of at most that many (golhip_step.cpp step_locked), and at that bound
     J = ceil(turns / D), j * D and turns - j * D fit an int for every depth
     the kernels take (1..64): checked here with g++ on csrc/gol_limits.h."""
     import os

@@ -1,7 +1,7 @@
 """Row-strip decomposition over torch.distributed (gloo, CPU): the N > 1 path.
 
 Each rank owns a strip of the 64x64 fixture torus and follows libgolhip's
-RCCL path (golhip.hip golhip_step / exchange_rccl): the library's own
+RCCL path (golhip_step.cpp golhip_step / exchange_rccl): the library's own
 golhip_halo_schedule (the same helper golhip_step calls, for both the
 per-launch and the resident kernel's schedule) says how deep the next exchange is (k launches of
 `depth` turns per exchange of k * depth rows), golhip_halo_plan which rows to
