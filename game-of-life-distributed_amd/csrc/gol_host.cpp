@@ -93,14 +93,11 @@ int env_int(const char *name, int dflt) {
 struct FlipBuffer {
     uint32_t *p = nullptr;
     uint64_t cap = 0;  // entries
-    void grow(uint64_t n) { grow_keep(n, 0); }
-    // at least n entries (doubling), the first `keep` entries preserved
-    void grow_keep(uint64_t n, uint64_t keep) {
+    // at least n entries (contents are not kept)
+    void grow(uint64_t n) {
         if (n <= cap) return;
-        if (keep) n = std::max<uint64_t>(n, 2 * cap);
         void *q = nullptr;
         check(golhip_host_alloc(n * sizeof(uint32_t), &q));
-        if (keep) memcpy(q, p, keep * sizeof(uint32_t));
         if (p) golhip_host_free(p);
         p = static_cast<uint32_t *>(q);
         cap = n;
@@ -220,35 +217,12 @@ struct Engine {
     }
     // Up to `want` turns with every turn's flip list as cell indices y * W + x
     // (golhip_flip_stream's contract: stops before a turn that does not fit;
-    // GOLHIP_ERANGE with *n = what the first turn needs).  Strips: one turn a
-    // group step; each strip's list of that turn is sized after the step
-    // (golhip_flips with cap 0) and the buffer grown to fit before the copy,
-    // so every turn runs and the buffer holds only what the lists need.
+    // GOLHIP_ERANGE with *n = what the first turn needs).  Strips: the same
+    // contract on the whole board (golhip_group_flip_stream).
     int flip_stream(int64_t want, FlipBuffer &fb, uint64_t *counts, int64_t *done, uint64_t *n) {
         if (one()) return golhip_flip_stream(hs[0], want, GOLHIP_FLIPS_INDEX, fb.p, fb.cap, counts, done, n);
-        *done = 0;
-        *n = 0;
-        std::vector<int32_t> xy;
-        for (int64_t t = 0; t < want; ++t) {
-            check(golhip_group_step_ex(hs.data(), (int32_t)hs.size(), 1, 1));
-            uint64_t turn_n = 0;
-            for (golhip_t h : hs) {
-                uint64_t k = 0;
-                int rc = golhip_flips(h, nullptr, 0, &k);
-                if (rc != GOLHIP_OK && rc != GOLHIP_ERANGE) check(rc);
-                if (k == 0) continue;
-                xy.resize(2 * k);
-                check(golhip_flips(h, xy.data(), k, &k));
-                fb.grow_keep(*n + turn_n + k, *n + turn_n);
-                for (uint64_t e = 0; e < k; ++e)
-                    fb.p[*n + turn_n + e] = (uint32_t)((uint64_t)xy[2 * e + 1] * (uint64_t)W + (uint64_t)xy[2 * e]);
-                turn_n += k;
-            }
-            counts[t] = turn_n;
-            *n += turn_n;
-            *done = t + 1;
-        }
-        return GOLHIP_OK;
+        return golhip_group_flip_stream(hs.data(), (int32_t)hs.size(), want, GOLHIP_FLIPS_INDEX, fb.p, fb.cap, counts, done,
+                                        n);
     }
 };
 

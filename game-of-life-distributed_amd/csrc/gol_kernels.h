@@ -253,6 +253,23 @@ struct FlipStreamArgs {
 };
 hipError_t launch_flip_stream(const FlipStreamArgs &a, hipStream_t s);
 int flip_turn_blocks_per_cu(bool contig);
+// golhip_group_flip_stream's gather: the batch's turns ran K5 on every strip
+// into the strip's own device list; this copies strip entries
+// [run[t], run[t + 1]) of every turn t < nturns to entry goff[t] of the
+// board's list `dst` (device-visible: golhip_host_alloc memory or a staging
+// buffer), where the strips' segments of a turn follow one another.  Source
+// and destination of a segment are aligned to an entry only: 16-byte stores
+// to the destination's boundaries, 4-byte loads, heads and tails.
+struct FlipGatherArgs {
+    const uint32_t *src;            // the strip's device list
+    uint32_t *dst;                  // the board's list
+    const unsigned long long *run;  // device: nturns + 1 running offsets of the strip's list (entries)
+    const unsigned long long *goff; // device: nturns destination offsets (entries)
+    int nturns;
+    unsigned wpe;                   // 32-bit words an entry (2: pairs, 1: indices)
+};
+// max_words: the longest segment (sizes the grid)
+hipError_t launch_flip_gather(const FlipGatherArgs &a, unsigned long long max_words, hipStream_t s);
 // gol_probe.hip: coalesced 16-byte stores over `bytes` (a multiple of 16) of
 // device-visible memory, e.g. page-locked host memory (the host-link probe)
 hipError_t launch_host_write_probe(void *dst, uint64_t bytes, int blocks, uint32_t tag, hipStream_t s);

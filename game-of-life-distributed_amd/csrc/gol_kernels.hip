@@ -2415,6 +2415,22 @@ __device__ __forceinline__ uint32_t ft_rule(const uint32_t (&w)[3], const uint32
     return bop<kNext>(u0, g1, g2);
 }
 
+// nw 32-bit words, device list `src` -> host list `d` (any 4-byte alignment
+// of either), by thread gt of gn (>= 3): 16-byte stores to the destination's
+// 16-byte boundaries from 4-byte loads, 4-byte heads and tails.
+__device__ __forceinline__ void ft_copy_words(uint32_t *d, const uint32_t *src, unsigned long long nw,
+                                              unsigned long long gt, unsigned long long gn) {
+    const unsigned long long head = min(nw, (unsigned long long)((4u - (unsigned)(((uintptr_t)d >> 2) & 3u)) & 3u));
+    const unsigned long long nq = (nw - head) / 4;
+    if (gt < head) d[gt] = src[gt];
+    for (unsigned long long q = gt; q < nq; q += gn) {
+        const unsigned long long w = head + 4 * q;
+        *reinterpret_cast<uint4 *>(d + w) = make_uint4(src[w], src[w + 1], src[w + 2], src[w + 3]);
+    }
+    const unsigned long long t0 = head + 4 * nq;
+    if (t0 + gt < nw) d[t0 + gt] = src[t0 + gt];
+}
+
 // The copy blocks of a K5 launch: the previous turn's entries, device list
 // -> host list, in 16-byte stores to the destination's 16-byte boundaries
 // (4-byte heads and tails), spread over the copy blocks.  They never wait on
@@ -2431,17 +2447,8 @@ __device__ void flip_copy_prev(const FlipTurnArgs &a, unsigned cb, unsigned ncb)
     const unsigned wpe = a.format == kFlipFormatXY ? 2u : 1u;  // 32-bit words per entry
     const uint32_t *src = reinterpret_cast<const uint32_t *>(a.out) + s * wpe;
     uint32_t *d = reinterpret_cast<uint32_t *>(a.cp_dst) + s * wpe;
-    const unsigned long long nw = (e - s) * wpe;
-    const unsigned long long head = min(nw, (unsigned long long)((4u - (unsigned)(((uintptr_t)d >> 2) & 3u)) & 3u));
-    const unsigned long long nq = (nw - head) / 4;
-    const unsigned long long gt = (unsigned long long)cb * kFtThreads + threadIdx.x, gn = (unsigned long long)ncb * kFtThreads;
-    if (gt < head) d[gt] = src[gt];
-    for (unsigned long long q = gt; q < nq; q += gn) {
-        const unsigned long long w = head + 4 * q;
-        *reinterpret_cast<uint4 *>(d + w) = make_uint4(src[w], src[w + 1], src[w + 2], src[w + 3]);
-    }
-    const unsigned long long t0 = head + 4 * nq;
-    if (t0 + gt < nw) d[t0 + gt] = src[t0 + gt];
+    ft_copy_words(d, src, (e - s) * wpe, (unsigned long long)cb * kFtThreads + threadIdx.x,
+                  (unsigned long long)ncb * kFtThreads);
 }
 
 // Shared memory of one K5 block.
@@ -3107,6 +3114,29 @@ hipError_t launch_flip_turn(const FlipTurnArgs &a, hipStream_t s) {
         hipLaunchKernelGGL(gol_flip_turn_kernel<true>, dim3((unsigned)grid), dim3(kFtThreads), 0, s, a);
     else
         hipLaunchKernelGGL(gol_flip_turn_kernel<false>, dim3((unsigned)grid), dim3(kFtThreads), 0, s, a);
+    return hipGetLastError();
+}
+
+// The gather of golhip_group_flip_stream: one strip's per-turn segments, device
+// list -> their places in the board's list (FlipGatherArgs).  Block row y
+// takes the turns t = y (mod gridDim.y), its gridDim.x blocks share a segment;
+// most segments are short or empty (a strip that flipped little in a turn).
+__global__ __launch_bounds__(256) void gol_flip_gather_kernel(FlipGatherArgs a) {
+    const unsigned long long gt = (unsigned long long)blockIdx.x * kFtThreads + threadIdx.x;
+    const unsigned long long gn = (unsigned long long)gridDim.x * kFtThreads;
+    for (int t = (int)blockIdx.y; t < a.nturns; t += (int)gridDim.y) {
+        const unsigned long long s = a.run[t], e = a.run[t + 1];
+        if (e <= s) continue;
+        ft_copy_words(a.dst + a.goff[t] * a.wpe, a.src + s * a.wpe, (e - s) * a.wpe, gt, gn);
+    }
+}
+
+hipError_t launch_flip_gather(const FlipGatherArgs &a, unsigned long long max_words, hipStream_t s) {
+    if (a.nturns <= 0 || max_words == 0) return hipSuccess;
+    // ~512 blocks: 8 K words of the longest segment a block, the rest over the turns
+    const unsigned gx = (unsigned)std::max<unsigned long long>(1, std::min<unsigned long long>(256, (max_words + 8191) / 8192));
+    const unsigned gy = (unsigned)std::max<int64_t>(1, std::min<int64_t>(a.nturns, 512 / gx));
+    hipLaunchKernelGGL(gol_flip_gather_kernel, dim3(gx, gy), dim3(kFtThreads), 0, s, a);
     return hipGetLastError();
 }
 

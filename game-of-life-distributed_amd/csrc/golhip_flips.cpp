@@ -1,6 +1,8 @@
 // golhip_flips.cpp — flip lists: the three-pass compaction (golhip_flips,
-// golhip_alive_cells) and the flip stream (K5 per turn, K5r resident).
+// golhip_alive_cells), the flip stream (K5 per turn, K5r resident) and the
+// stream of a group of row strips (K5 per strip and turn, one gather a strip).
 #include "golhip_impl.h"
+#include "gol_flip_merge.h"
 #include <climits>
 #include <cstdlib>
 
@@ -181,6 +183,33 @@ static int flip_resident_batch(golhip_t h, const FlipBatch &b, int ncopy, uint64
     return GOLHIP_OK;
 }
 
+// Turn t of a batch: one K5 launch (the halo rows, if used, already in place).
+static int flip_turn_launch(golhip_t h, const FlipBatch &b, int64_t t, bool overlap, int cpb) {
+    const bool last = t == b.nlaunch - 1;
+    if (last) HIP_OR_FAIL(hipMemsetAsync(h->d_scalars, 0, sizeof(unsigned long long), h->stream));
+    golk::FlipTurnArgs a = flip_turn_args(h, b, true);
+    a.src = h->buf[h->cur];
+    a.dst = h->buf[h->cur ^ 1];
+    a.out = b.direct && !overlap ? b.direct : (void *)h->d_ev.p;
+    a.cp_run = overlap && t > 0 ? h->d_run.p + t - 1 : nullptr;
+    a.cp_dst = b.direct;
+    a.cp_blocks = cpb;
+    a.run = h->d_run.p + t;
+    a.ticket = h->d_ftticket.p + t;
+    h->flip_epoch = (h->flip_epoch + 1) & 0x3FFFFFu;
+    if (h->flip_epoch == 0) h->flip_epoch = 1;  // 0 is the zeroed status array's epoch
+    a.epoch = h->flip_epoch;
+    a.coresident = b.coresident ? 1 : 0;
+    a.alive = last ? h->d_scalars : nullptr;
+    if (int rc = span_begin(h, h->stream)) return rc;
+    HIP_OR_FAIL(golk::launch_flip_turn(a, h->stream));
+    if (int rc = span_end(h, 2)) return rc;
+    h->n.flip_launches++;
+    h->cur ^= 1;
+    h->turns += 1;
+    return GOLHIP_OK;
+}
+
 // One K5 launch per turn.  overlap (flip_overlap 1): each launch's `cpb` copy
 // blocks move the previous turn's list to the host, and a copy-only launch
 // the last turn's; else the turn's own blocks store into `out` (direct) or d_ev.
@@ -188,28 +217,7 @@ static int flip_turn_loop(golhip_t h, const FlipBatch &b, bool overlap, int cpb)
     for (int64_t t = 0; t < b.nlaunch; ++t) {
         if (b.halo)
             if (int rc = exchange_rccl(h, 1, h->stream)) return rc;
-        const bool last = t == b.nlaunch - 1;
-        if (last) HIP_OR_FAIL(hipMemsetAsync(h->d_scalars, 0, sizeof(unsigned long long), h->stream));
-        golk::FlipTurnArgs a = flip_turn_args(h, b, true);
-        a.src = h->buf[h->cur];
-        a.dst = h->buf[h->cur ^ 1];
-        a.out = b.direct && !overlap ? b.direct : (void *)h->d_ev.p;
-        a.cp_run = overlap && t > 0 ? h->d_run.p + t - 1 : nullptr;
-        a.cp_dst = b.direct;
-        a.cp_blocks = cpb;
-        a.run = h->d_run.p + t;
-        a.ticket = h->d_ftticket.p + t;
-        h->flip_epoch = (h->flip_epoch + 1) & 0x3FFFFFu;
-        if (h->flip_epoch == 0) h->flip_epoch = 1;  // 0 is the zeroed status array's epoch
-        a.epoch = h->flip_epoch;
-        a.coresident = b.coresident ? 1 : 0;
-        a.alive = last ? h->d_scalars : nullptr;
-        if (int rc = span_begin(h, h->stream)) return rc;
-        HIP_OR_FAIL(golk::launch_flip_turn(a, h->stream));
-        if (int rc = span_end(h, 2)) return rc;
-        h->n.flip_launches++;
-        h->cur ^= 1;
-        h->turns += 1;
+        if (int rc = flip_turn_launch(h, b, t, overlap, cpb)) return rc;
     }
     if (overlap && b.nlaunch > 0) {  // the last turn's list: a copy-only launch
         golk::FlipTurnArgs a = flip_turn_args(h, b, false);
@@ -381,6 +389,246 @@ static int flip_stream_locked(golhip_t h, int64_t nturns, int format, void *out,
     return GOLHIP_OK;
 }
 
+// ---- golhip_group_flip_stream: the stream of a board held as row strips ----
+
+// One entry of the caller's list from an (x, y) pair.
+static inline void put_entry(void *out, int format, uint64_t at, int32_t x, int32_t y, int W) {
+    if (format == GOLHIP_FLIPS_XY) {
+        static_cast<int32_t *>(out)[2 * at] = x;
+        static_cast<int32_t *>(out)[2 * at + 1] = y;
+    } else {
+        static_cast<uint32_t *>(out)[at] = (uint32_t)((uint64_t)y * (uint64_t)W + (uint64_t)x);
+    }
+}
+
+static int group_sync(golhip_t *hs, int n) {
+    for (int i = 0; i < n; ++i) {
+        if (int rc = set_dev(hs[i])) return rc;
+        if (int rc = sync_stream(hs[i])) return rc;
+    }
+    return GOLHIP_OK;
+}
+
+// Generic widths and giant strips: one group turn at a time through the
+// three-pass compaction, the board's count checked on the host before the
+// turn's entries are fetched (two synchronisations a turn); a turn that does
+// not fit is undone on every strip (its source board is still the other buffer).
+static int group_flip_generic(golhip_t *hs, int n, int64_t nturns, int format, void *out, uint64_t cap, uint64_t *counts,
+                              hipEvent_t *ready, int64_t *done_out, uint64_t *total_out) {
+    std::vector<std::vector<int32_t>> xy((size_t)n);
+    std::vector<uint64_t> k((size_t)n);
+    uint64_t acc = 0, need = 0;
+    int64_t t = 0;
+    for (; t < nturns; ++t) {
+        if (int rc = group_step_locked(hs, n, 1, 1, ready)) return rc;
+        for (int i = 0; i < n; ++i) {
+            golhip *h = hs[i];
+            if (int rc = set_dev(h)) return rc;
+            HIP_OR_FAIL(hipMemcpyAsync(h->h_scalars + 1, h->d_scalars + 1, 8, hipMemcpyDeviceToHost, h->stream));
+        }
+        if (int rc = group_sync(hs, n)) return rc;
+        uint64_t c = 0;
+        for (int i = 0; i < n; ++i) c += k[i] = hs[i]->h_scalars[1];
+        if (c > cap - acc) {
+            for (int i = 0; i < n; ++i) {
+                hs[i]->cur ^= 1;
+                hs[i]->turns -= 1;
+                hs[i]->alive_turn = -1;
+                hs[i]->flips_valid = false;
+            }
+            need = c;
+            break;
+        }
+        for (int i = 0; i < n; ++i) {
+            golhip *h = hs[i];
+            if (k[i] == 0) continue;
+            if (int rc = set_dev(h)) return rc;
+            if (int rc = ensure_xy(h, (int64_t)k[i])) return rc;
+            HIP_OR_FAIL(golk::launch_compact_scatter(h->cur_rows(), h->prev_rows(), h->local_words(), h->Ww, h->row0,
+                                                     h->d_blk.p, h->d_xy.p, h->il, h->stream));
+            xy[i].resize(2 * k[i]);
+            HIP_OR_FAIL(hipMemcpyAsync(xy[i].data(), h->d_xy.p, k[i] * 8, hipMemcpyDeviceToHost, h->stream));
+        }
+        if (int rc = group_sync(hs, n)) return rc;
+        for (int i = 0; i < n; ++i) {
+            for (uint64_t e = 0; e < k[i]; ++e) put_entry(out, format, acc + e, xy[i][2 * e], xy[i][2 * e + 1], hs[0]->W);
+            acc += k[i];
+            hs[i]->n.flip_entries += (int64_t)k[i];
+        }
+        counts[t] = c;
+    }
+    *done_out = t;
+    *total_out = t == 0 ? need : acc;
+    return GOLHIP_OK;
+}
+
+// W % 32 == 0: per turn the group's 1-row halo exchange, then K5 on every
+// strip's stream into the strip's own device list with its own running
+// offsets (no strip waits for another's); nothing is synchronised in the turn
+// loop.  Then the run arrays come back (first synchronisation), the merge
+// plan (gol_flip_merge.h) places the segments, one gather launch a strip
+// moves them into `out` (second synchronisation).  K5 runs in ticket order:
+// strips that share a device share its CUs, so no strip's grid is known to
+// be resident at once.
+static int group_flip_fused(golhip_t *hs, int n, int64_t nturns, int format, void *out, uint64_t cap, uint64_t *counts,
+                            hipEvent_t *ready, int64_t *done_out, uint64_t *total_out) {
+    const int esz = format == GOLHIP_FLIPS_XY ? 8 : 4;
+    golhip *g = hs[0];  // keeps the group's estimate and staging buffer
+    // launch the turns the buffer certainly held at the last batch's largest
+    // turn: a batch that stops early costs a restore and a re-run
+    int64_t nlaunch = nturns;
+    if (g->group_ft_est > 0) nlaunch = std::max<int64_t>(1, std::min<int64_t>(nturns, (int64_t)(cap / g->group_ft_est)));
+    const int64_t t0 = g->turns;
+    std::vector<FlipBatch> bs((size_t)n);
+    std::vector<int> c0((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        golhip *h = hs[i];
+        if (int rc = set_dev(h)) return rc;
+        if (int rc = set_layout(h, 0)) return rc;
+        h->flips_valid = false;
+        FlipBatch &b = bs[i];
+        b.nturns = nturns;
+        b.format = format;
+        b.cap = cap;
+        b.stop = true;
+        b.esz = esz;
+        b.nw = h->local_words();
+        const uint64_t most = (uint64_t)nlaunch * (uint64_t)h->W * (uint64_t)h->rows;
+        b.dcap = std::min<uint64_t>({cap, most, (uint64_t)INT64_MAX / 16});
+        b.nb = golk::flip_turn_blocks(b.nw);
+        b.nlaunch = nlaunch;
+        b.coresident = false;
+        b.sa = step_args(h, nullptr, n > 1);
+        c0[i] = h->cur;
+        if (int rc = h->d_run.ensure(h, nlaunch + 1)) return rc;
+        if (int rc = h->d_goff.ensure(h, nlaunch)) return rc;
+        if (int rc = h->d_ftstatus.ensure(h, 3 * b.nb, true)) return rc;
+        if (int rc = h->d_ftticket.ensure(h, nlaunch)) return rc;
+        if (int rc = h->d_ftctl.ensure(h, 2)) return rc;
+        if (int rc = h->d_ev.ensure(h, (int64_t)std::max<uint64_t>(b.dcap, 1) * esz)) return rc;
+        if (nlaunch > 1) {  // the board to restore when the batch stops early
+            if (int rc = h->backup.ensure(h, h->local_words())) return rc;
+            HIP_OR_FAIL(hipMemcpyAsync(h->backup.p, h->cur_rows(), (size_t)h->local_words() * 4, hipMemcpyDeviceToDevice,
+                                       h->stream));
+        }
+        HIP_OR_FAIL(hipMemsetAsync(h->d_run.p, 0, (size_t)(nlaunch + 1) * sizeof(unsigned long long), h->stream));
+        HIP_OR_FAIL(hipMemsetAsync(h->d_ftticket.p, 0, (size_t)nlaunch * sizeof(unsigned), h->stream));
+        HIP_OR_FAIL(hipMemsetAsync(h->d_ftctl.p, 0, 2 * sizeof(unsigned), h->stream));
+    }
+    for (int64_t t = 0; t < nlaunch; ++t) {
+        if (n > 1)
+            if (int rc = group_exchange(hs, n, 1, ready, false)) return rc;
+        for (int i = 0; i < n; ++i) {
+            if (int rc = set_dev(hs[i])) return rc;
+            if (int rc = flip_turn_launch(hs[i], bs[i], t, false, 0)) return rc;
+        }
+    }
+    // first synchronisation: every strip's running offsets and flags
+    std::vector<unsigned long long> runs((size_t)n * (size_t)(nlaunch + 1));
+    std::vector<unsigned> ctl(2 * (size_t)n);
+    for (int i = 0; i < n; ++i) {
+        golhip *h = hs[i];
+        if (int rc = set_dev(h)) return rc;
+        HIP_OR_FAIL(hipMemcpyAsync(runs.data() + (size_t)i * (size_t)(nlaunch + 1), h->d_run.p,
+                                   (size_t)(nlaunch + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+        HIP_OR_FAIL(hipMemcpyAsync(ctl.data() + 2 * i, h->d_ftctl.p, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+    }
+    if (int rc = group_sync(hs, n)) return rc;
+    for (int i = 0; i < n; ++i)
+        if (ctl[2 * i + 1]) return fail(GOLHIP_EHIP, "group flip stream: look-back spin bound exceeded on strip %d (board undefined)", i);
+    const FlipMergePlan plan = flip_merge_plan(runs.data(), n, nlaunch, cap);
+    const int64_t done = plan.done;
+    if (done == nlaunch) {
+        for (int i = 0; i < n; ++i) hs[i]->alive_turn = hs[i]->turns;
+    } else if (done == nlaunch - 1) {
+        // only the last turn did not fit: no strip stopped before it, so every
+        // strip ran it on valid halos and its source board is the other buffer
+        for (int i = 0; i < n; ++i) {
+            hs[i]->cur ^= 1;
+            hs[i]->turns = t0 + done;
+            hs[i]->alive_turn = -1;
+        }
+    } else {
+        // a strip that passed cap by itself stopped there while the others went
+        // on beside its stale rows: the boards past turn `done` are void.
+        // Restore the batch's first board and step `done` turns (their lists,
+        // complete on every strip, are delivered below)
+        for (int i = 0; i < n; ++i) {
+            golhip *h = hs[i];
+            if (int rc = set_dev(h)) return rc;
+            HIP_OR_FAIL(hipMemcpyAsync(h->buf[c0[i]] + (int64_t)kHalo * h->Ww, h->backup.p, (size_t)h->local_words() * 4,
+                                       hipMemcpyDeviceToDevice, h->stream));
+            h->cur = c0[i];
+            h->turns = t0;
+            h->alive_turn = -1;
+        }
+        if (done > 0)
+            if (int rc = group_step_locked(hs, n, done, 0, ready)) return rc;
+    }
+    // the gather: strip i's segments of the delivered turns to their places in
+    // `out`, written by the strip's device where `out` is mapped on it, else
+    // into a page-locked list of the batch that the host copies from
+    if (plan.total > 0) {
+        int mapped_dev = -1;
+        char *mapped = (char *)mapped_device_ptr(out, (size_t)plan.total * esz, &mapped_dev);
+        bool staged = false;
+        for (int i = 0; i < n; ++i) staged |= !(mapped && hs[i]->device == mapped_dev);
+        if (staged && g->g_stage_bytes < plan.total * esz) {
+            if (g->g_stage) HIP_OR_FAIL(hipHostFree(g->g_stage));
+            g->g_stage = nullptr;
+            g->g_stage_bytes = 0;
+            const size_t want = std::max<size_t>((size_t)plan.total * esz, 1 << 16);
+            if (hipError_t e = hipHostMalloc(&g->g_stage, want, hipHostMallocPortable | hipHostMallocMapped); e != hipSuccess) {
+                g->g_stage = nullptr;
+                return fail(GOLHIP_ENOMEM, "hipHostMalloc(%zu): %s", want, hipGetErrorString(e));
+            }
+            g->g_stage_bytes = want;
+        }
+        for (int i = 0; i < n; ++i) {
+            golhip *h = hs[i];
+            if (runs[(size_t)i * (size_t)(nlaunch + 1) + (size_t)done] == 0) continue;  // nothing of this strip
+            if (int rc = set_dev(h)) return rc;
+            const bool direct = mapped && h->device == mapped_dev;
+            void *dst = mapped;
+            if (!direct) HIP_OR_FAIL(hipHostGetDevicePointer(&dst, g->g_stage, 0));
+            HIP_OR_FAIL(hipMemcpyAsync(h->d_goff.p, plan.goff.data() + (size_t)i * (size_t)nlaunch,
+                                       (size_t)done * sizeof(unsigned long long), hipMemcpyHostToDevice, h->stream));
+            golk::FlipGatherArgs a{};
+            a.src = reinterpret_cast<const uint32_t *>(h->d_ev.p);
+            a.dst = static_cast<uint32_t *>(dst);
+            a.run = h->d_run.p;
+            a.goff = h->d_goff.p;
+            a.nturns = (int)done;
+            a.wpe = (unsigned)esz / 4;
+            if (int rc = span_begin(h, h->stream)) return rc;
+            HIP_OR_FAIL(golk::launch_flip_gather(a, plan.max_seg * a.wpe, h->stream));
+            if (int rc = span_end(h, 2)) return rc;
+        }
+        // second synchronisation
+        if (int rc = group_sync(hs, n)) return rc;
+        if (staged && !mapped) {
+            memcpy(out, g->g_stage, (size_t)plan.total * esz);
+        } else if (staged) {
+            for (int i = 0; i < n; ++i) {
+                if (hs[i]->device == mapped_dev) continue;
+                const unsigned long long *r = runs.data() + (size_t)i * (size_t)(nlaunch + 1);
+                for (int64_t t = 0; t < done; ++t) {
+                    const size_t at = (size_t)plan.goff[(size_t)i * (size_t)nlaunch + (size_t)t] * esz;
+                    memcpy((char *)out + at, (char *)g->g_stage + at, (size_t)(r[t + 1] - r[t]) * esz);
+                }
+            }
+        }
+    } else if (done < nlaunch) {
+        if (int rc = group_sync(hs, n)) return rc;
+    }
+    for (int i = 0; i < n; ++i) hs[i]->n.flip_entries += (int64_t)runs[(size_t)i * (size_t)(nlaunch + 1) + (size_t)done];
+    for (int64_t t = 0; t < done; ++t) counts[t] = plan.counts[(size_t)t];
+    if (done > 0) g->group_ft_est = plan.most;
+    *done_out = done;
+    *total_out = done == 0 ? plan.need : plan.total;
+    return GOLHIP_OK;
+}
+
 }  // namespace gh
 
 using namespace gh;
@@ -450,6 +698,55 @@ int golhip_flip_stream(golhip_t h, int64_t nturns, int32_t format, void *out, ui
     *turns_done = done;
     *n = total;
     if (nturns > 0 && done == 0)
+        return fail(GOLHIP_ERANGE, "buffer holds %llu entries, the next turn needs %llu", (unsigned long long)cap,
+                    (unsigned long long)total);
+    return GOLHIP_OK;
+}
+
+int golhip_group_flip_stream(golhip_t *hs, int32_t n, int64_t nturns, int32_t format, void *out, uint64_t cap,
+                             uint64_t *counts, int64_t *turns_done, uint64_t *n_entries) {
+    if (n_entries) *n_entries = 0;
+    if (turns_done) *turns_done = 0;
+    if (int rc = group_check(hs, n)) return rc;
+    if (n == 1 && hs[0]->torus()) return golhip_flip_stream(hs[0], nturns, format, out, cap, counts, turns_done, n_entries);
+    if (nturns < 0) return fail(GOLHIP_EINVAL, "nturns %lld", (long long)nturns);
+    if (format != GOLHIP_FLIPS_XY && format != GOLHIP_FLIPS_INDEX) return fail(GOLHIP_EINVAL, "format %d", format);
+    if (nturns > 0 && (!counts || !turns_done || !n_entries)) return fail(GOLHIP_EINVAL, "counts / turns_done / n_entries is null");
+    if (cap > 0 && !out) return fail(GOLHIP_EINVAL, "out is null");
+    if (format == GOLHIP_FLIPS_INDEX && (uint64_t)hs[0]->W * (uint64_t)hs[0]->H > (1ull << 32))
+        return fail(GOLHIP_EINVAL, "cell indices of a %dx%d board do not fit in 32 bits", hs[0]->W, hs[0]->H);
+    std::vector<std::unique_lock<std::mutex>> locks;
+    for (int i = 0; i < n; ++i) locks.emplace_back(hs[i]->mu);
+    bool fused = hs[0]->W % 32 == 0;
+    for (int i = 0; i < n; ++i) {
+        if (hs[i]->turns != hs[0]->turns)
+            return fail(GOLHIP_EINVAL, "strip %d is at turn %lld, strip 0 at turn %lld", i, (long long)hs[i]->turns,
+                        (long long)hs[0]->turns);
+        if (want_il(hs[i]) != want_il(hs[0])) return fail(GOLHIP_EINVAL, "strip %d uses another word layout", i);
+        fused &= hs[i]->local_words() < (1ll << 32) - 4096;
+    }
+    if (nturns == 0) return GOLHIP_OK;
+    // group_exchange's events, made once for the call
+    std::vector<hipEvent_t> ready((size_t)n, nullptr);
+    int rc = GOLHIP_OK;
+    for (int i = 0; i < n; ++i) {
+        HIP_RC(hipSetDevice(hs[i]->device));
+        HIP_RC(hipEventCreateWithFlags(&ready[i], hipEventDisableTiming));
+    }
+    int64_t done = 0;
+    uint64_t total = 0;
+    if (!rc)
+        rc = fused ? group_flip_fused(hs, n, nturns, format, out, cap, counts, ready.data(), &done, &total)
+                   : group_flip_generic(hs, n, nturns, format, out, cap, counts, ready.data(), &done, &total);
+    for (int i = 0; i < n; ++i) {  // (an error may have left work behind the events)
+        HIP_RC(hipSetDevice(hs[i]->device));
+        if (rc) (void)hipStreamSynchronize(hs[i]->stream);
+        if (ready[i]) HIP_RC(hipEventDestroy(ready[i]));
+    }
+    if (rc) return rc;
+    *turns_done = done;
+    *n_entries = total;
+    if (done == 0)
         return fail(GOLHIP_ERANGE, "buffer holds %llu entries, the next turn needs %llu", (unsigned long long)cap,
                     (unsigned long long)total);
     return GOLHIP_OK;

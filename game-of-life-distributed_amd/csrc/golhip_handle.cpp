@@ -354,6 +354,8 @@ int golhip_destroy(golhip_t h) {
     HIP_RC(hipFree(h->d_ftctl.p));
     HIP_RC(hipFree(h->d_ftdone.p));
     HIP_RC(hipFree(h->d_ev.p));
+    HIP_RC(hipFree(h->d_goff.p));
+    if (h->g_stage) HIP_RC(hipHostFree(h->g_stage));
     HIP_RC(hipFree(h->d_stage.p));
     HIP_RC(hipFree(h->d_vcount.p));
     HIP_RC(hipFree(h->d_sync));

@@ -16,7 +16,7 @@
 //   golhip_handle.cpp   handle lifetime, board I/O, counts, hash, perf, trace
 //   golhip_plan.cpp     launch planners (decisions on integers + occupancy caches)
 //   golhip_step.cpp     step launches, resident guard, RCCL ring, group step
-//   golhip_flips.cpp    flip lists and the flip stream (K5, K5r)
+//   golhip_flips.cpp    flip lists and the flip stream (K5, K5r; a group of strips: K5 + gather)
 //   golhip_view.cpp     live view of one handle and of a group of strips (K7)
 //   golhip_options.cpp  the option table and its consent rules
 //
@@ -204,6 +204,11 @@ struct golhip {
     bool ft_ticket = false;       // K5 block order by ticket (set after a co-residency failure)
     uint64_t ft_est = 0;          // most entries of one turn in the last batch (launch sizing)
     int64_t flip_fallbacks = 0;
+    // golhip_group_flip_stream (the staging list and the estimate live on the group's first strip)
+    gh::DevScratch<unsigned long long> d_goff;  // this strip's segment offsets in `out`, one a turn
+    void *g_stage = nullptr;      // page-locked list of a batch whose `out` the strips' devices cannot write
+    size_t g_stage_bytes = 0;
+    uint64_t group_ft_est = 0;    // most entries of one board turn in the last batch (launch sizing)
     gh::DevScratch<uint8_t> d_stage;    // byte staging for load/snapshot
     gh::DevScratch<uint32_t> d_vcount;  // group view: count rows of the pixel rows that straddle strips
     bool flips_valid = false;
@@ -316,6 +321,12 @@ int launch_depth(golhip_t h, int depth, bool count, bool halo);
 int step_checked_locked(golhip_t h, int64_t nturns, int32_t want_flips);
 int group_check(golhip_t *hs, int32_t n);
 int group_step_locked(golhip_t *hs, int32_t n, int64_t nturns, int32_t want_flips, hipEvent_t *keep = nullptr);
+// Halo rows of every strip from its ring neighbours' current boards, x rows
+// each way, by peer copies ordered through the n events `ready`.  relaunch:
+// several launches may follow before the next exchange, so every stream also
+// waits for its neighbours' copies (false: exactly one single-turn launch a
+// strip follows, as in the group flip stream).
+int group_exchange(golhip_t *hs, int32_t n, int x, hipEvent_t *ready, bool relaunch = true);
 
 // ---- golhip_flips.cpp -------------------------------------------------------
 int start_flips(golhip_t h);

@@ -510,6 +510,49 @@ int group_check(golhip_t *hs, int32_t n) {
     return GOLHIP_OK;
 }
 
+// Halo rows of every strip from its ring neighbours' current boards: x rows
+// each way (every strip's mutex held; ready: one event a strip).  relaunch:
+// more than one launch follows the exchange (see below).
+int group_exchange(golhip_t *hs, int32_t n, int x, hipEvent_t *ready, bool relaunch) {
+    int rc = GOLHIP_OK;
+    for (int i = 0; i < n && !rc; ++i) {
+        HIP_RC(hipSetDevice(hs[i]->device));
+        HIP_RC(hipEventRecord(ready[i], hs[i]->stream));
+    }
+    for (int i = 0; i < n && !rc; ++i) {
+        golhip *me = hs[i], *prev = hs[(i - 1 + n) % n], *next = hs[(i + 1) % n];
+        golhip_halo_plan_t p;
+        halo_plan(me->rows, n, i, x, me->Ww, &p);
+        HIP_RC(hipSetDevice(me->device));
+        HIP_RC(hipStreamWaitEvent(me->stream, ready[(i - 1 + n) % n], 0));
+        HIP_RC(hipStreamWaitEvent(me->stream, ready[(i + 1) % n], 0));
+        const size_t bytes = (size_t)p.bytes;
+        // top halo <- prev's last x rows; bottom halo <- next's first x rows
+        uint32_t *mb = me->buf[me->cur];
+        const uint32_t *pb = prev->buf[prev->cur] + (int64_t)(kHalo + prev->rows - x) * prev->Ww;
+        const uint32_t *nb = next->buf[next->cur] + (int64_t)kHalo * next->Ww;
+        HIP_RC(hipMemcpyPeerAsync(mb + (int64_t)p.recv_top_row * me->Ww, me->device, pb, prev->device, bytes,
+                                  me->stream));
+        HIP_RC(hipMemcpyPeerAsync(mb + (int64_t)p.recv_bottom_row * me->Ww, me->device, nb, next->device,
+                                  bytes, me->stream));
+        me->n.halo_bytes += 2 * (int64_t)bytes;
+    }
+    // a strip's second launch rewrites the buffer its neighbours copied
+    // from: every stream waits for its neighbours' copies first.  (One launch
+    // an exchange writes the other buffer, and the next exchange's first
+    // waits order the launch after it behind these copies.)
+    for (int i = 0; i < n && !rc && relaunch; ++i) {
+        HIP_RC(hipSetDevice(hs[i]->device));
+        HIP_RC(hipEventRecord(ready[i], hs[i]->stream));
+    }
+    for (int i = 0; i < n && !rc && relaunch; ++i) {
+        HIP_RC(hipSetDevice(hs[i]->device));
+        HIP_RC(hipStreamWaitEvent(hs[i]->stream, ready[(i - 1 + n) % n], 0));
+        HIP_RC(hipStreamWaitEvent(hs[i]->stream, ready[(i + 1) % n], 0));
+    }
+    return rc;
+}
+
 // The step of a checked group with every strip's mutex held.  `keep`
 // (golhip_group_view_stream): the caller's n events, left alive, and no
 // synchronisation at the end: the caller synchronises every stream and takes
@@ -527,41 +570,8 @@ int group_step_locked(golhip_t *hs, int32_t n, int64_t nturns, int32_t want_flip
         if (!rc) rc = set_layout(hs[i], want_il(hs[i]));
         hs[i]->flips_valid = false;
     }
-    // halo rows of every strip from its ring neighbours' current boards: x rows each way
     auto exchange = [&](int x) {
-        for (int i = 0; i < n && !rc; ++i) {
-            HIP_RC(hipSetDevice(hs[i]->device));
-            HIP_RC(hipEventRecord(ready[i], hs[i]->stream));
-        }
-        for (int i = 0; i < n && !rc; ++i) {
-            golhip *me = hs[i], *prev = hs[(i - 1 + n) % n], *next = hs[(i + 1) % n];
-            golhip_halo_plan_t p;
-            halo_plan(me->rows, n, i, x, me->Ww, &p);
-            HIP_RC(hipSetDevice(me->device));
-            HIP_RC(hipStreamWaitEvent(me->stream, ready[(i - 1 + n) % n], 0));
-            HIP_RC(hipStreamWaitEvent(me->stream, ready[(i + 1) % n], 0));
-            const size_t bytes = (size_t)p.bytes;
-            // top halo <- prev's last x rows; bottom halo <- next's first x rows
-            uint32_t *mb = me->buf[me->cur];
-            const uint32_t *pb = prev->buf[prev->cur] + (int64_t)(kHalo + prev->rows - x) * prev->Ww;
-            const uint32_t *nb = next->buf[next->cur] + (int64_t)kHalo * next->Ww;
-            HIP_RC(hipMemcpyPeerAsync(mb + (int64_t)p.recv_top_row * me->Ww, me->device, pb, prev->device, bytes,
-                                      me->stream));
-            HIP_RC(hipMemcpyPeerAsync(mb + (int64_t)p.recv_bottom_row * me->Ww, me->device, nb, next->device,
-                                      bytes, me->stream));
-            me->n.halo_bytes += 2 * (int64_t)bytes;
-        }
-        // a strip's second launch rewrites the buffer its neighbours copied
-        // from: every stream waits for its neighbours' copies first
-        for (int i = 0; i < n && !rc; ++i) {
-            HIP_RC(hipSetDevice(hs[i]->device));
-            HIP_RC(hipEventRecord(ready[i], hs[i]->stream));
-        }
-        for (int i = 0; i < n && !rc; ++i) {
-            HIP_RC(hipSetDevice(hs[i]->device));
-            HIP_RC(hipStreamWaitEvent(hs[i]->stream, ready[(i - 1 + n) % n], 0));
-            HIP_RC(hipStreamWaitEvent(hs[i]->stream, ready[(i + 1) % n], 0));
-        }
+        if (!rc) rc = group_exchange(hs, n, x, ready.data());
     };
     const int64_t tail = (want_flips && nturns > 0) ? 1 : 0;
     int64_t left = nturns - tail;

@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("GOLHIP_LIB") or os.path.join(HERE, "libgolhip.so")  #
 HEADER = os.path.join(HERE, "..", "..", "include", "golhip.h")
 
 GOLHIP_OK = 0
+GOLHIP_EINVAL = -1
 GOLHIP_ERANGE = -4
 FLIPS_XY, FLIPS_INDEX = 0, 1
 FLAG_TIMING = 0x1
@@ -153,6 +154,8 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "golhip_step_flips": ([H, i64, ctypes.c_void_p, u64, ctypes.c_void_p, P(u64)], ctypes.c_int),
         "golhip_alive_cells": ([H, ctypes.c_void_p, u64, P(u64)], ctypes.c_int),
         "golhip_flip_stream": ([H, i64, i32, ctypes.c_void_p, u64, ctypes.c_void_p, P(i64), P(u64)], ctypes.c_int),
+        "golhip_group_flip_stream": ([P(H), i32, i64, i32, ctypes.c_void_p, u64, ctypes.c_void_p, P(i64), P(u64)],
+                                     ctypes.c_int),
         "golhip_snapshot_bytes": ([H, ctypes.c_void_p], ctypes.c_int),
         "golhip_snapshot_bits": ([H, ctypes.c_void_p], ctypes.c_int),
         "golhip_snapshot_rows": ([H, i32, i32, ctypes.c_void_p], ctypes.c_int),
@@ -514,6 +517,25 @@ def group_step(boards: list[Board], nturns: int, want_flips: bool = False) -> No
         _check(load().golhip_group_step_ex(arr, len(boards), nturns, 1))
     else:
         _check(load().golhip_group_step(arr, len(boards), nturns))
+
+
+def group_flip_stream(boards: list[Board], nturns: int, cap: int, fmt: int = FLIPS_XY, out: np.ndarray | None = None):
+    """golhip_group_flip_stream: Board.flip_stream of the whole board that the
+    strips `boards` (the group of group_step) hold: (entries, counts,
+    turns_done), each turn's list row-major over the whole board in global
+    coordinates; every strip is left at the same turn.  `out` may be a
+    host_array the gather kernels write themselves."""
+    shape, dt = ((cap, 2), np.int32) if fmt == FLIPS_XY else ((cap,), np.uint32)
+    if out is None:
+        out = np.empty((max(cap, 1),) + shape[1:], dtype=dt)
+    if out.shape[0] < cap or out.dtype != dt or not out.flags.c_contiguous:
+        raise ValueError("out must be a C-contiguous array of >= cap entries")
+    counts = np.zeros(max(nturns, 1), dtype=np.uint64)
+    done, n = ctypes.c_int64(), ctypes.c_uint64()
+    arr = (ctypes.c_void_p * len(boards))(*[b.handle for b in boards])
+    _check(load().golhip_group_flip_stream(arr, len(boards), nturns, fmt, _ptr(out), cap, _ptr(counts),
+                                           ctypes.byref(done), ctypes.byref(n)))
+    return out[: n.value], counts[: done.value], done.value
 
 
 def _group_view(boards, x0, y0, scale, out_w, out_h, fmt) -> View:

@@ -316,6 +316,24 @@ int golhip_step_flips(golhip_t h, int64_t nturns, int32_t *xy, uint64_t cap, uin
 #define GOLHIP_FLIPS_INDEX 1
 int golhip_flip_stream(golhip_t h, int64_t nturns, int32_t format, void *out, uint64_t cap, uint64_t *counts,
                        int64_t *turns_done, uint64_t *n);
+/* golhip_flip_stream of the whole board held by the group of row strips `hs`
+ * (the group golhip_group_step takes; every strip at the same turn, else
+ * GOLHIP_EINVAL): the same contract, word for word.  Up to nturns turns one at
+ * a time; each turn's list is appended to `out` in turn order, row-major over
+ * the whole torus within a turn (strip order), coordinates global; counts[t]
+ * is the board's count of turn t; the batch stops before the first turn whose
+ * board-wide list would not fit in cap entries and leaves EVERY strip at that
+ * turn (golhip_group_step / golhip_step* continue from there); if not even the
+ * first turn fits: GOLHIP_ERANGE, nothing advanced, *n_entries = what it
+ * needs.  widths that are a multiple of 32: K5 per strip and turn into device
+ * lists, no host synchronisation between turns, then one gather launch a
+ * strip that writes `out` itself where it lies in golhip_host_alloc memory
+ * mapped on the strip's device: two host round trips a call.  Other widths:
+ * one group turn at a time (two round trips a turn).  With n == 1 and a
+ * whole-torus handle it is golhip_flip_stream.  In-process groups only (not
+ * multi-rank rings). */
+int golhip_group_flip_stream(golhip_t *hs, int32_t n, int64_t nturns, int32_t format, void *out, uint64_t cap,
+                             uint64_t *counts, int64_t *turns_done, uint64_t *n_entries);
 /* Alive cells, row-major (x = col, y = row) pairs — calculateAliveCells. */
 int golhip_alive_cells(golhip_t h, int32_t *xy, uint64_t cap, uint64_t *n);
 /* Board as 0/255 bytes / bit words (this handle's rows). */

@@ -46,7 +46,10 @@ package gol
 //                                 uint64_t *n) {
 //     return gh_wrap(golhip_flip_stream(h, t, GOLHIP_FLIPS_INDEX, out, cap, counts, done, n));
 // }
-// static gh_status gh_flips(golhip_t h, int32_t *xy, uint64_t cap, uint64_t *n) { return gh_wrap(golhip_flips(h, xy, cap, n)); }
+// static gh_status gh_group_flip_stream(golhip_t *hs, int32_t n, int64_t t, void *out, uint64_t cap, uint64_t *counts,
+//                                       int64_t *done, uint64_t *total) {
+//     return gh_wrap(golhip_group_flip_stream(hs, n, t, GOLHIP_FLIPS_INDEX, out, cap, counts, done, total));
+// }
 // static gh_status gh_alive_cells(golhip_t h, int32_t *xy, uint64_t cap, uint64_t *n) {
 //     return gh_wrap(golhip_alive_cells(h, xy, cap, n));
 // }
@@ -93,7 +96,6 @@ type engine struct {
 	flipsP unsafe.Pointer // golhip_host_alloc buffer of cell indices y*width + x
 	flips  []uint32       // a Go view of it
 	counts []uint64       // per-turn list lengths of the last flipStream
-	xy     []int32        // strips: one strip's flip pairs of a turn
 
 	framesP unsafe.Pointer // golhip_host_alloc buffer of view frames (ARGB8888)
 	frames  []uint32       // a Go view of it
@@ -226,12 +228,13 @@ func (e *engine) flipStream(n int) (int, []uint64, []uint32) {
 	if len(e.counts) < n {
 		e.counts = make([]uint64, n)
 	}
-	if len(e.hs) > 1 {
-		return e.stripFlipStream(n)
-	}
 	var done C.int64_t
 	var total C.uint64_t
 	call := func() C.gh_status {
+		if len(e.hs) > 1 { // row strips: the same contract on the whole board (golhip_group_flip_stream)
+			return C.gh_group_flip_stream((*C.golhip_t)(unsafe.Pointer(&e.hs[0])), C.int32_t(len(e.hs)), C.int64_t(n),
+				e.flipsP, C.uint64_t(len(e.flips)), (*C.uint64_t)(unsafe.Pointer(&e.counts[0])), &done, &total)
+		}
 		return C.gh_flip_stream(e.hs[0], C.int64_t(n), e.flipsP, C.uint64_t(len(e.flips)),
 			(*C.uint64_t)(unsafe.Pointer(&e.counts[0])), &done, &total)
 	}
@@ -242,62 +245,6 @@ func (e *engine) flipStream(n int) (int, []uint64, []uint32) {
 	}
 	check(st)
 	return int(done), e.counts[:int(done)], e.flips[:int(total)]
-}
-
-// stripFlipStream: group turns one at a time (golhip_group_step_ex keeps each
-// strip's list of that turn after the step), each strip's list sized first
-// (golhip_flips with cap 0) and the buffer grown to fit before it is copied,
-// the strips' lists appended in strip order.  Runs all n turns; the buffer
-// only ever grows to what the lists need (no worst-case W x H reservation).
-func (e *engine) stripFlipStream(n int) (int, []uint64, []uint32) {
-	total := 0
-	for done := 0; done < n; done++ {
-		e.group(1, 1)
-		turnN := 0
-		for _, h := range e.hs {
-			var k C.uint64_t
-			if st := C.gh_flips(h, nil, 0, &k); st.rc != C.GOLHIP_OK && st.rc != C.GOLHIP_ERANGE {
-				check(st)
-			}
-			if k == 0 {
-				continue
-			}
-			if len(e.xy) < 2*int(k) {
-				e.xy = make([]int32, 2*int(k))
-			}
-			check(C.gh_flips(h, (*C.int32_t)(unsafe.Pointer(&e.xy[0])), k, &k))
-			if need := total + turnN + int(k); need > len(e.flips) {
-				e.growFlipsKeep(need, total+turnN)
-			}
-			for i := 0; i < int(k); i++ {
-				e.flips[total+turnN+i] = uint32(int(e.xy[2*i+1])*e.width + int(e.xy[2*i]))
-			}
-			turnN += int(k)
-		}
-		e.counts[done] = uint64(turnN)
-		total += turnN
-	}
-	return n, e.counts[:n], e.flips[:total]
-}
-
-// growFlipsKeep grows the flip buffer to at least n entries (doubling),
-// keeping its first `keep` entries.
-func (e *engine) growFlipsKeep(n int, keep int) {
-	if n <= len(e.flips) {
-		return
-	}
-	if n < 2*len(e.flips) {
-		n = 2 * len(e.flips)
-	}
-	var p unsafe.Pointer
-	check(C.gh_host_alloc(C.uint64_t(n*4), &p))
-	nf := (*[1 << 32]uint32)(p)[:n:n]
-	copy(nf, e.flips[:keep])
-	if e.flipsP != nil {
-		C.golhip_host_free(e.flipsP)
-	}
-	e.flipsP = p
-	e.flips = nf
 }
 
 // aliveCells is calculateAliveCells (distributor.go:420-432): Cell{X: col, Y: row}, row-major.

@@ -19,6 +19,19 @@ Prints one JSON object with:
 Every leg starts from the same state (seed 0x5EED0005 + 2064 turns: ~0.4 M
 flips a turn; the first turns of the random board flip 3-7 M) and runs the
 same 200 turns, so the flip totals must agree (checked).
+
+--strips N: instead of the above, the event stream of a board held as row
+strips (golhip_group_flip_stream) into page-locked memory, cell indices:
+512^2 (the fixture image) on 3 strips for 10000 turns and 5120^2 (the state
+above) on N strips for 1000 turns.  Per shape, three alternating runs each of
+  group_stream   golhip_group_flip_stream, as many turns a call as a 32 M-entry
+                 buffer holds
+  turn_loop      a group step of one turn with want_flips, then golhip_flips
+                 on every strip (what gol.Run's strips branch did before)
+  single_stream  golhip_flip_stream of one whole-torus handle: the ceiling
+from the same state, after a 20-turn warm-up of each: turns/s (host clock
+around calls that end synchronised), the flip totals and index sums (must
+agree; they are summed outside the timed calls).  One JSON object.
 """
 import json
 import os
@@ -39,6 +52,87 @@ TURNS = 200
 HBM_PEAK = 8.0e12
 out = {"workload": "configs[4]: 5120^2 random 25%, seed 0x5EED0005, turns 2065..2264", "board": [N, N]}
 
+
+def strips_mode(nstrips):
+    res = {"mode": "strips", "format": "index", "buffer_entries": 32 << 20, "shapes": []}
+    with np.load(os.path.join(ROOT, "tests", "golden", "fixtures.npz"), allow_pickle=False) as z:
+        from oracle.oracle import unpack_bits
+        image = unpack_bits(z["image_512"], 512)
+    cap = 32 << 20
+    buf = golhip.host_array((cap,), np.uint32)
+    buf.fill(0)
+    for W, n, turns, pre in ((512, 3, 10000, 0), (N, nstrips, 1000, 2064)):
+        cuts = [W * i // n for i in range(n + 1)]
+        strips = [golhip.Board(W, W, row0=a, rows=b - a) for a, b in zip(cuts[:-1], cuts[1:])]
+        whole = golhip.Board(W, W)
+
+        def reset():
+            for st, a, b in zip(strips, cuts[:-1], cuts[1:]):
+                st.load_bytes(image[a:b]) if pre == 0 else st.fill_random(SEED)
+            whole.load_bytes(image) if pre == 0 else whole.fill_random(SEED)
+            if pre:
+                golhip.group_step(strips, pre)
+                whole.step(pre)
+            for st in strips + [whole]:
+                st.sync()
+
+        # (seconds: the engine calls alone; the digests are taken outside them)
+        def stream(call, t):
+            done = flips = calls = digest = 0
+            secs = 0.0
+            while done < t:
+                t0 = time.perf_counter()
+                ent, counts, k = call(t - done)
+                secs += time.perf_counter() - t0
+                done, flips, calls = done + k, flips + len(ent), calls + 1
+                digest += int(ent.sum(dtype=np.uint64))
+            return flips, digest, calls, secs
+
+        def group_stream(t):
+            return stream(lambda k: golhip.group_flip_stream(strips, k, cap=cap, fmt=golhip.FLIPS_INDEX, out=buf), t)
+
+        def single_stream(t):
+            return stream(lambda k: whole.flip_stream(k, cap=cap, fmt=golhip.FLIPS_INDEX, out=buf), t)
+
+        def turn_loop(t):
+            flips = digest = 0
+            secs = 0.0
+            for _ in range(t):
+                t0 = time.perf_counter()
+                golhip.group_step(strips, 1, want_flips=True)
+                lists = [st.flips() for st in strips]
+                secs += time.perf_counter() - t0
+                for xy in lists:
+                    flips += len(xy)
+                    if len(xy):
+                        digest += int((xy[:, 1].astype(np.uint64) * np.uint64(W) + xy[:, 0].astype(np.uint64)).sum())
+            return flips, digest, t, secs
+
+        methods = (("group_stream", group_stream), ("turn_loop", turn_loop), ("single_stream", single_stream))
+        reset()
+        for _, fn in methods:  # warm-up: code objects, scratch buffers, the stream's launch estimate
+            fn(20)
+        rec = {"board": [W, W], "strips": n, "turns": turns, "from_turn": pre, "runs": {k: [] for k, _ in methods}}
+        for _ in range(3):
+            for name, fn in methods:
+                reset()
+                flips, digest, calls, dt = fn(turns)
+                rec["runs"][name].append({"seconds": dt, "turns_per_s": turns / dt, "flips": flips,
+                                          "index_sum": digest, "calls": calls})
+        same = {(r["flips"], r["index_sum"]) for rs in rec["runs"].values() for r in rs}
+        rec["same_lists"] = len(same) == 1
+        for name, rs in rec["runs"].items():
+            v = sorted(r["turns_per_s"] for r in rs)
+            rec[name + "_turns_per_s"] = {"min": v[0], "median": v[1], "max": v[2]}
+        res["shapes"].append(rec)
+        for st in strips + [whole]:
+            st.close()
+    print(json.dumps(res))
+
+
+if "--strips" in sys.argv:
+    strips_mode(int(sys.argv[sys.argv.index("--strips") + 1]))
+    sys.exit(0)
 
 # the host link itself: one 64 MiB device -> host copy, pageable vs page-locked
 # (torch first: its HIP runtime must initialise before libgolhip's does)
