@@ -192,6 +192,10 @@ int depth_cap(golhip_t h, bool halo) {
         if (skew_dims(h, 20, 2, h->rows, &sk) && sk.half) cap = 16;
     }
     if (cap == 9 && (wpl != 4 || (halo && persist_on(h)))) cap = 8;  // only per-launch quads have 9
+    // only the pair rule has 18 (depth_plan would take a cap of exactly 18 as
+    // its own): a tb_depth of 18, or a schedule planned from 18 rows, at one
+    // word per lane has no kernel at all
+    if (cap == 18 && !pair) cap = 16;
     // quads (bit 2): 8 turns a launch on the pair rule instead of 9 on the 9-LUT stages
     if ((h->skew_pairs & 2) && wpl == 4 && cap >= 8) {
         golk::SkewArgs sk{};
@@ -257,9 +261,10 @@ static int skew_bpc(golhip_t h, int depth, int wpl, bool half, bool pr) {
 // The stack plan of a K1w launch over L rows: tiles, workgroup shape, stacks
 // and tile kind (no side effects); false if K1w does not apply.
 bool skew_dims(golhip_t h, int depth, int wpl, int L, golk::SkewArgs *sk) {
-    // the pair rule: 18 turns at two words per lane (no other kernel runs 18,
-    // depth_cap), 8 at four (option "skew_pairs" bit 2)
-    const bool pr = depth == 18 || (wpl == 4 && depth == 8 && (h->skew_pairs & 2));
+    // the pair rule: 18 turns at two words per lane (option "skew_pairs" bit
+    // 1; no other K1w runs 18: a strip whose group plans 18 without the bit
+    // takes the per-launch kernel), 8 at four (bit 2)
+    const bool pr = (depth == 18 && (h->skew_pairs & 1)) || (wpl == 4 && depth == 8 && (h->skew_pairs & 2));
     if (!h->skew || h->W % 32 != 0 || !golk::skew_supported(depth, wpl, false, pr)) return false;
     const int hcap = h->skew_hcap >= 0 ? h->skew_hcap : 3 * depth / 4;
     const int smin = depth + 3;

@@ -117,6 +117,39 @@ def test_halo_schedule_covers_turns(tb):
         assert len(seq) <= g
 
 
+KERNEL_DEPTHS = {1, 2, 4, 6, 8, 9, 12, 16, 18, 20, 24, 32}  # golhip_impl.h kDepths
+
+
+def test_halo_schedule_exhaustive_properties():
+    """Every golhip_halo_schedule answer for strips of 1..40 rows, tb_depth
+    1..32, both kernels and 1..150 turns left names a depth the kernels are
+    instantiated at, within the strip, the halo rows and the turns left; the
+    depths of one word width alone (9: quads, 18: the pair rule) only under a
+    cap of exactly them; and the rounds add up to the turns asked for."""
+    lib = golhip.load()
+    d, k = ctypes.c_int32(), ctypes.c_int32()
+    pd, pk = ctypes.byref(d), ctypes.byref(k)
+    LEFT = 150
+    for rows in range(1, 41):
+        for tb in range(1, golhip.MAX_TB_DEPTH + 1):
+            cap = min(tb, rows)
+            for resident in (0, 1):
+                rounds = [0] * (LEFT + 1)  # rounds[l]: exchanges that l turns take (0 turns: none)
+                for left in range(1, LEFT + 1):
+                    assert lib.golhip_halo_schedule(rows, tb, resident, left, pd, pk) == 0
+                    dv, kv = d.value, k.value
+                    where = (rows, tb, resident, left, dv, kv)
+                    assert dv in KERNEL_DEPTHS, where
+                    assert dv <= cap, where
+                    assert dv not in (9, 18) or cap == dv, where
+                    assert 1 <= kv <= max(1, rows // dv), where
+                    assert kv * dv <= min(golhip.HALO_ROWS, left), where
+                    # the next call is the one for left - k d turns (checked above):
+                    # the schedule from `left` ends at exactly 0 turns left
+                    rounds[left] = rounds[left - kv * dv] + 1
+                assert all(1 <= rounds[l] <= l for l in range(1, LEFT + 1))
+
+
 def test_product_build_macros():
     """The shipped libgolhip.so is built with the default tuning macros: no
     A/B or layout-experiment build (GOL_LOOP_PAD etc.) is mistaken for the

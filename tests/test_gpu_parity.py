@@ -22,7 +22,7 @@ pytestmark = pytest.mark.gpu
 golhip = pytest.importorskip("golhip")
 
 CHECKS = [(16, 0), (16, 1), (16, 100), (64, 0), (64, 1), (64, 100), (512, 0), (512, 1), (512, 100)]
-DEPTHS = [1, 2, 4, 6, 8, 12, 16, 20, 24, 32]
+DEPTHS = [1, 2, 4, 6, 8, 9, 12, 16, 18, 20, 24, 32]
 
 
 @pytest.fixture(scope="module")
@@ -217,6 +217,13 @@ def test_step_flips_capacity_and_edges(fixtures):
 @pytest.mark.parametrize("fill_skip", [0, 1])
 @pytest.mark.parametrize("wpl", [1, 2, 4])
 def test_depth_and_strip_height_invariance(fixtures, depth, rpw, fill_skip, wpl):
+    """The options must not change the result, whichever kernel they reach.
+    `persistent` is left at auto, so on this 256 x 256 torus one and two words
+    per lane run all 70 turns as one resident K1r launch (measured:
+    lds_launches 1, step_launches 0 at every depth, rows_per_wave and
+    fill_skip); only four words per lane reaches the per-launch kernels here
+    (launches of at most 9 turns).  The per-launch instantiations are pinned
+    one by one in tests/test_gpu_plan_closure.py."""
     board = img(fixtures, 256)
     assert np.array_equal(run_gpu(board, 70, depth, rpw, fill_skip=fill_skip, wpl=wpl), run_np(board, 70))
 
