@@ -155,7 +155,10 @@ hipError_t launch_pack(const uint8_t *bytes, uint32_t *words, int W, int Ww, int
 // (W % 64 == 0); pack / fill_random / load write canonical words, which the
 // engine converts in place with launch_convert_layout.
 hipError_t launch_unpack(const uint32_t *words, uint8_t *bytes, int W, int Ww, int rows, int il, hipStream_t s);
+// `words` 16-byte aligned, or (layouts 0 and 2, nwords even) 8-byte aligned.
 hipError_t launch_convert_layout(uint32_t *words, int64_t nwords, int from, int to, hipStream_t s);
+// Clears the bits of columns >= W in the last word of each row (W % 32 != 0).
+hipError_t launch_clear_row_tail(uint32_t *words, int W, int Ww, int rows, hipStream_t s);
 hipError_t launch_fill_random(uint32_t *words, int W, int Ww, int rows, int64_t row0, uint64_t seed,
                               hipStream_t s);
 hipError_t launch_popcount(const uint32_t *words, int64_t nwords, unsigned long long *out, hipStream_t s);

@@ -73,10 +73,33 @@ __global__ __launch_bounds__(256) void convert_layout_kernel(uint32_t *__restric
     reinterpret_cast<uint4 *>(w)[i] = make_uint4(x[0], x[1], x[2], x[3]);
 }
 
+// The same, one pair of words per thread (layouts 0 and 2): for a row range
+// that starts on an even word but not on a 16-byte boundary
+// (golhip_snapshot_rows, tests/test_gpu_io_edges.py).
+__global__ __launch_bounds__(256) void convert_pairs_kernel(uint32_t *__restrict__ w, int64_t npairs, int from, int to) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npairs) return;
+    uint2 *p = reinterpret_cast<uint2 *>(w) + i;
+    const uint2 v = *p;
+    uint32_t a = v.x, b = v.y, e, o;
+    if (from == 2) il_decode(v.x, v.y, a, b);
+    if (to == 2) il_encode(a, b, e, o);
+    else e = a, o = b;
+    *p = make_uint2(e, o);
+}
+
 hipError_t launch_convert_layout(uint32_t *words, int64_t nwords, int from, int to, hipStream_t s) {
     if (from == to) return hipSuccess;
     const int64_t nq = (nwords + 3) / 4;
     if (nq == 0) return hipSuccess;
+    if (reinterpret_cast<uintptr_t>(words) % 16 != 0) {
+        // whole boards are 16-byte aligned; a row range of the pair layout (rows of whole pairs) need not be
+        if (reinterpret_cast<uintptr_t>(words) % 8 != 0 || nwords % 2 != 0 || from == 4 || to == 4)
+            return hipErrorInvalidValue;
+        const int64_t np = nwords / 2;
+        hipLaunchKernelGGL(convert_pairs_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s, words, np, from, to);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(convert_layout_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, words, nwords, from, to);
     return hipGetLastError();
 }
@@ -3206,6 +3229,22 @@ hipError_t launch_unpack(const uint32_t *words, uint8_t *bytes, int W, int Ww, i
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(unpack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, words, bytes, W, Ww,
                        rows, il);
+    return hipGetLastError();
+}
+
+// Bit words from a caller (golhip_load_bits): the bits of columns >= W in the
+// last word of each row are no cells and are cleared (W % 32 != 0 only).
+__global__ __launch_bounds__(256) void clear_row_tail_kernel(uint32_t *__restrict__ words, int Ww, int rows,
+                                                              uint32_t keep) {
+    const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= rows) return;
+    words[row * Ww + (Ww - 1)] &= keep;
+}
+
+hipError_t launch_clear_row_tail(uint32_t *words, int W, int Ww, int rows, hipStream_t s) {
+    if (W % 32 == 0 || rows == 0) return hipSuccess;
+    hipLaunchKernelGGL(clear_row_tail_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, words, Ww, rows,
+                       (1u << (W % 32)) - 1u);
     return hipGetLastError();
 }
 

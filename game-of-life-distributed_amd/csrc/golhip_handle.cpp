@@ -52,9 +52,12 @@ int set_dev(golhip_t h) {
     return GOLHIP_OK;
 }
 
-// Rows per launch chunk for byte staging (<= 64 MiB of bytes).
+// Rows per launch chunk for byte staging (<= kStageBytes of bytes; one buffer
+// reused chunk after chunk).  Boards past one chunk, with a one-row last
+// chunk: tests/test_gpu_io_edges.py::test_chunked_byte_io.
+static constexpr int64_t kStageBytes = 64ll << 20;
 static int64_t stage_rows(golhip_t h) {
-    const int64_t per = std::max<int64_t>(1, (64ll << 20) / std::max(1, h->W));
+    const int64_t per = std::max<int64_t>(1, kStageBytes / std::max(1, h->W));
     return std::min<int64_t>(per, h->rows);
 }
 
@@ -409,6 +412,8 @@ int golhip_load_bits(golhip_t h, const uint32_t *words) {
     std::lock_guard<std::mutex> g(h->mu);
     if (int rc = set_dev(h)) return rc;
     HIP_OR_FAIL(hipMemcpyAsync(h->cur_rows(), words, (size_t)h->local_words() * 4, hipMemcpyHostToDevice, h->stream));
+    // the caller's bits of columns >= width are no cells (golhip.h): popcount, hash and K3 run over whole words
+    HIP_OR_FAIL(golk::launch_clear_row_tail(h->cur_rows(), h->W, h->Ww, h->rows, h->stream));
     if (int rc = loaded_canonical(h)) return rc;
     if (int rc_ = sync_stream(h)) return rc_;
     h->turns = 0;
@@ -517,6 +522,7 @@ int golhip_snapshot_rows(golhip_t h, int32_t row, int32_t nrows, uint32_t *out) 
     std::lock_guard<std::mutex> g(h->mu);
     if (int rc = set_dev(h)) return rc;
     // a row holds whole pairs / quads in their layouts, so the range converts alone
+    // (a pair-layout row may start 8 bytes off a 16-byte boundary: launch_convert_layout goes by pairs then)
     uint32_t *p = h->cur_rows() + (int64_t)row * h->Ww;
     const int64_t n = (int64_t)nrows * h->Ww;
     HIP_OR_FAIL(golk::launch_convert_layout(p, n, h->il, 0, h->stream));

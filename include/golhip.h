@@ -270,6 +270,10 @@ int golhip_halo_schedule(int32_t strip_rows, int32_t tb_depth, int32_t resident,
 /* ---- board I/O -------------------------------------------------------- */
 /* Load this handle's rows (height x width bytes, or its strip's rows). */
 int golhip_load_bytes(golhip_t h, const uint8_t *cells);
+/* The same rows as bit words (rows x ceil(width/32) uint32, cell (y, x) = bit
+ * x % 32 of word x / 32 of row y).  Where width % 32 != 0 the bits of columns
+ * >= width in the last word of a row are ignored: they are cleared on the
+ * device after the copy, so no count, digest, list or snapshot sees them. */
 int golhip_load_bits(golhip_t h, const uint32_t *words);
 /* Synthetic board: cell (y, x) alive <=> (splitmix64(seed ^ (y*width + x)) & 3) == 0,
  * global coordinates (strips of one board agree). */
