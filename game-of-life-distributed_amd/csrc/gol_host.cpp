@@ -171,7 +171,26 @@ struct Engine {
         }
     }
     ~Engine() {
+        if (ckpt) golhip_checkpoint_wait(ckpt, nullptr);
         for (golhip_t h : hs) golhip_destroy(h);
+    }
+    // The checkpoint in flight (RunOptions::checkpoint_path): at most one.
+    golhip_ckpt *ckpt = nullptr;
+    int64_t ckpt_turn = -1;  // turn of the last checkpoint begun
+    void ckpt_wait() {
+        if (!ckpt) return;
+        golhip_ckpt *c = ckpt;
+        ckpt = nullptr;
+        check(golhip_checkpoint_wait(c, nullptr));
+    }
+    void ckpt_begin(const std::string &path, int64_t turn) {
+        ckpt_wait();
+        check(golhip_checkpoint_begin(hs.data(), (int32_t)hs.size(), path.c_str(), nullptr, &ckpt));
+        ckpt_turn = turn;
+    }
+    // board and turn from a checkpoint file (RunOptions::resume_path)
+    void resume(const std::string &path) {
+        check(golhip_checkpoint_load(hs.data(), (int32_t)hs.size(), path.c_str(), nullptr, nullptr));
     }
     bool one() const { return hs.size() == 1; }
     int64_t rows(size_t i) const { return (i + 1 < row0.size() ? row0[i + 1] : H) - row0[i]; }
@@ -234,13 +253,38 @@ void Run(Params p, Chan<Event> *events, Chan<char32_t> *keyPresses, const RunOpt
     const std::string name = std::to_string(W) + "x" + std::to_string(H);
     const bool quirks = opt.ref_quirks;
 
-    // distributor.go:39-41 -> io.readPgmImage
-    std::vector<uint8_t> raster = ReadPgm(opt.root + "/images/" + name + ".pgm", W, H);
-    std::printf("File %s input done!\n", name.c_str());
-    std::fflush(stdout);
+    const bool ckpt_on = !opt.checkpoint_path.empty();
+    if (opt.checkpoint_every < 0 || (opt.checkpoint_every > 0 && !ckpt_on))
+        throw std::runtime_error("checkpoint_every must be >= 0 and needs checkpoint_path");
+
+    // distributor.go:39-41 -> io.readPgmImage; a resumed run takes board and
+    // turn from its checkpoint instead (and fails where readPgmImage fails)
+    int64_t T0 = 0;
+    std::vector<uint8_t> raster;
+    if (opt.resume_path.empty()) {
+        raster = ReadPgm(opt.root + "/images/" + name + ".pgm", W, H);
+        std::printf("File %s input done!\n", name.c_str());
+        std::fflush(stdout);
+    } else {
+        golhip_ckpt_info_t ci;
+        check(golhip_checkpoint_info(opt.resume_path.c_str(), &ci));
+        if (ci.width != W) throw std::runtime_error("Incorrect width");
+        if (ci.height != H) throw std::runtime_error("Incorrect height");
+        if (ci.turn > p.Turns)
+            throw std::runtime_error("checkpoint " + opt.resume_path + " is at turn " + std::to_string(ci.turn) +
+                                     ", past the run's " + std::to_string(p.Turns) + " turns");
+        T0 = ci.turn;
+    }
 
     Engine board(W, H, opt);
-    board.load(raster.data());
+    if (opt.resume_path.empty()) {
+        board.load(raster.data());
+    } else {
+        board.resume(opt.resume_path);
+        std::printf("Checkpoint %s input done! (turn %lld)\n", opt.resume_path.c_str(), (long long)T0);
+        std::fflush(stdout);
+    }
+    std::vector<uint8_t>().swap(raster);
 
     // Live view: frames land in the ring and are published by pointer.  With
     // cell events the turns keep the flip stream, in batches that end on the
@@ -288,19 +332,20 @@ void Run(Params p, Chan<Event> *events, Chan<char32_t> *keyPresses, const RunOpt
         return fname;
     };
 
-    // distributor.go:72-80: CellFlipped for every cell alive at load, turn 0.
+    // distributor.go:72-80: CellFlipped for every cell alive at load, turn 0
+    // (a resumed run: the checkpoint's board, at its turn).
     if (opt.cell_events && events)
         for (const util::Cell &c : board.cells(golhip_alive_cells, quirks)) {
             Event e;
             e.kind = EventKind::CellFlipped;
-            e.CompletedTurns = 0;
+            e.CompletedTurns = T0;
             e.Cell = c;
             send(e);
         }
 
     std::mutex mu;                 // the reference's `mu`: held by the turn loop and by pause
     std::atomic<int> waiters{0};   // helpers queued for `mu` (std::mutex is not fair)
-    std::atomic<int64_t> turn{0};  // completed turns
+    std::atomic<int64_t> turn{T0};  // completed turns
     // helpers take `mu` through this, so the turn loop can step aside for them
     auto lock_mu = [&]() {
         ++waiters;
@@ -365,6 +410,10 @@ void Run(Params p, Chan<Event> *events, Chan<char32_t> *keyPresses, const RunOpt
                     auto g = lock_mu();  // snapshot at a turn boundary
                     t = turn.load();
                     fname = write_snapshot(t, quirks);
+                    // with checkpointing on, the turn loop sees it before its next call: the
+                    // run stops at the snapshot's turn, the turn of the take-over checkpoint
+                    // (without, `q` is raised after the event below, as it always was)
+                    if (k == U'q' && ckpt_on) quit = true;
                 }
                 Event e;
                 e.kind = EventKind::ImageOutputComplete;
@@ -435,16 +484,24 @@ void Run(Params p, Chan<Event> *events, Chan<char32_t> *keyPresses, const RunOpt
         std::vector<uint64_t> counts((size_t)batch);
         constexpr uint64_t kFlipChunk = 4096;
         std::vector<Event> flip_evs;
-        int64_t t = 0;
+        int64_t t = T0;
         while (t < p.Turns && !quit.load()) {
             int64_t want = std::min<int64_t>(batch, p.Turns - t);
+            // an engine call ends on every checkpoint turn
+            if (opt.checkpoint_every > 0) want = std::min(want, opt.checkpoint_every - t % opt.checkpoint_every);
             if (view_on && !view_stream) want = std::min(want, opt.view_every - t % opt.view_every);  // end on a frame turn
+            // a view stream's frames stay on the multiples of view_every: a call begun off one (behind
+            // a checkpoint turn or a resume; never otherwise) steps to the next and renders there
+            const bool streamed = view_stream && t % opt.view_every == 0;
+            if (view_stream && !streamed) want = std::min(want, opt.view_every - t % opt.view_every);
             int64_t done = want;
             uint64_t n = 0;
             int view_half = 0;
+            bool ckpt_due = false;
             {
                 std::lock_guard<std::mutex> g(mu);
-                if (view_stream) {
+                if (quit.load()) break;  // `q` took its snapshot while this thread waited for `mu`
+                if (streamed) {
                     // frame i of the batch shows turn t + (i + 1) * every
                     uint64_t nf = 0;
                     view_half = ring->half;
@@ -464,7 +521,15 @@ void Run(Params p, Chan<Event> *events, Chan<char32_t> *keyPresses, const RunOpt
                 }
                 t += done;
                 turn = t;
-                if (view_on && !view_stream && t % opt.view_every == 0) view_now();  // ahead of the batch's events
+                if (view_on && !streamed && t % opt.view_every == 0) view_now();  // ahead of the batch's events
+                ckpt_due = opt.checkpoint_every > 0 && done > 0 && t % opt.checkpoint_every == 0;
+            }
+            if (ckpt_due) {
+                // the previous checkpoint's writer (fsync, rename) is joined off `mu`, so the ticker and the
+                // keys are not held up by the file system; only the enqueue is a turn-boundary action
+                board.ckpt_wait();
+                std::lock_guard<std::mutex> g(mu);
+                board.ckpt_begin(opt.checkpoint_path, t);
             }
             // let a queued ticker / key handler take `mu` before the next batch
             while (waiters.load() > 0) std::this_thread::sleep_for(std::chrono::microseconds(20));
@@ -491,7 +556,7 @@ void Run(Params p, Chan<Event> *events, Chan<char32_t> *keyPresses, const RunOpt
                     }
                     off += n;
                 }
-                if (view_stream && (i + 1) % opt.view_every == 0)  // (t0 is a multiple of every)
+                if (streamed && (i + 1) % opt.view_every == 0)  // (t0 is a multiple of every)
                     opt.view_sink->publish(ring->slot(view_half, (i + 1) / opt.view_every - 1), ring->frame_bytes,
                                            completed);
                 if (opt.turn_events) {
@@ -506,7 +571,12 @@ void Run(Params p, Chan<Event> *events, Chan<char32_t> *keyPresses, const RunOpt
         if (view_on && opt.view_sink->turn() != turn.load()) view_now();  // turns after the last frame
         if (quit.load()) {
             // `q` (:244-261): snapshot already written; the reference os.Exit(0)s
-            // without FinalTurnComplete.  The mirror ends the run instead.
+            // without FinalTurnComplete.  The mirror ends the run instead; with
+            // checkpointing on it first leaves the state a new controller takes over.
+            if (ckpt_on) {
+                if (board.ckpt_turn != turn.load()) board.ckpt_begin(opt.checkpoint_path, turn.load());
+                board.ckpt_wait();
+            }
             Event e;
             e.kind = EventKind::StateChange;
             e.CompletedTurns = turn.load();
@@ -515,6 +585,7 @@ void Run(Params p, Chan<Event> *events, Chan<char32_t> *keyPresses, const RunOpt
             if (events) events->close();
             return;
         }
+        board.ckpt_wait();  // the last periodic checkpoint is on disk before FinalTurnComplete
         // distributor.go:180-206
         std::vector<util::Cell> alive = board.cells(golhip_alive_cells, false);
         const std::string fname = write_snapshot(p.Turns, false);
@@ -593,8 +664,26 @@ int golrun_view_frame(golrun_t r, void *out, uint64_t cap_bytes, int64_t *turn) 
 int golrun_start_view(int64_t turns, int64_t threads, int64_t width, int64_t height, const char *root,
                       int32_t device, uint32_t flags, int32_t events_cap, int32_t ticker_ms,
                       const golhip_view_t *view, int32_t every, golrun_t *out) {
+    golrun_opts_t opts;
+    memset(&opts, 0, sizeof opts);
+    opts.view = view;
+    opts.view_every = every;
+    return golrun_start_opts(turns, threads, width, height, root, device, flags, events_cap, ticker_ms, &opts, out);
+}
+
+int golrun_start_opts(int64_t turns, int64_t threads, int64_t width, int64_t height, const char *root,
+                      int32_t device, uint32_t flags, int32_t events_cap, int32_t ticker_ms,
+                      const golrun_opts_t *opts, golrun_t *out) {
     if (!out || !root || events_cap < 0) return run_fail("bad arguments");
+    golrun_opts_t none;
+    memset(&none, 0, sizeof none);
+    none.view_every = 1;
+    if (!opts) opts = &none;
+    const golhip_view_t *view = opts->view;
+    const int32_t every = opts->view_every;
     if (view && (view->scale < 1 || every < 1)) return run_fail("view scale and every must be >= 1");
+    if (opts->checkpoint_every < 0 || (opts->checkpoint_every > 0 && !(opts->checkpoint_path && *opts->checkpoint_path)))
+        return run_fail("checkpoint_every must be >= 0 and needs checkpoint_path");
     gol::Params p;
     p.Turns = turns;
     p.Threads = threads;
@@ -607,6 +696,9 @@ int golrun_start_view(int64_t turns, int64_t threads, int64_t width, int64_t hei
     o.cell_events = (flags & GOLRUN_FLAG_NO_CELL_EVENTS) == 0;
     o.turn_events = (flags & GOLRUN_FLAG_NO_TURN_EVENTS) == 0;
     if (ticker_ms > 0) o.ticker_seconds = ticker_ms / 1000.0;
+    if (opts->checkpoint_path) o.checkpoint_path = opts->checkpoint_path;
+    o.checkpoint_every = opts->checkpoint_every;
+    if (opts->resume_path) o.resume_path = opts->resume_path;
     golrun *r = new golrun((size_t)events_cap, (flags & GOLRUN_FLAG_KEYS) != 0);
     if (flags & GOLRUN_FLAG_VIEW_STRIPS) o.view_strips = 1;
     if (view) {

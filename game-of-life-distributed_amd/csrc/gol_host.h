@@ -408,6 +408,21 @@ struct RunOptions {
     int view_strips = -1;
     int64_t view_every = 1;
     ViewSink *view_sink = nullptr;
+    // Checkpoint and resume (fault tolerance as restart in a new process; the
+    // reference README's "a new controller should be able to take over").
+    // checkpoint_path: a checkpoint file (golhip_checkpoint_begin) is written
+    // there at every turn that is a multiple of checkpoint_every (0: none), an
+    // engine call ending on each such turn and the file draining behind the
+    // following turns; the run waits for one before it begins the next, and
+    // for the last before FinalTurnComplete.  On `q` it writes one of the turn
+    // it stops at and waits for it before StateChange{Quitting}.
+    // resume_path: the board and its turn T come from that checkpoint instead
+    // of images/<W>x<H>.pgm (its size must equal Params, T <= Params.Turns;
+    // Run throws otherwise, before any event).  The initial CellFlipped events
+    // are that board's alive cells at turn T, TurnComplete continues at T + 1.
+    std::string checkpoint_path;
+    int64_t checkpoint_every = 0;
+    std::string resume_path;
 };
 
 // The PGM goroutine's file formats (io.go:42-126).

@@ -313,6 +313,17 @@ struct ViewResolveArgs {
 };
 hipError_t launch_view_resolve(ViewResolveArgs a, hipStream_t s);
 
+// gol_ckpt.hip (K8): the canonical words of the nwords words `rows` (layout
+// il; read only) to `shadow`, with sums[0] += their alive count and sums[1] +=
+// their golhip_board_hash digest (word0: global index of word 0).  Both
+// buffers 16-byte aligned; nwords a multiple of il where il > 0.
+hipError_t launch_ckpt(const uint32_t *rows, uint32_t *shadow, int64_t nwords, int64_t word0, int il,
+                       unsigned long long *sums, hipStream_t s);
+// The inverse: canonical words `stage` into `rows` in layout il, the bits of
+// columns >= W cleared; sums as above, of the words stored.
+hipError_t launch_ckpt_load(const uint32_t *stage, uint32_t *rows, int64_t nwords, int64_t word0, int W, int Ww, int il,
+                            unsigned long long *sums, hipStream_t s);
+
 // "NAME=value ..." of the build's tuning macros (golhip_build_info).
 const char *build_info();
 

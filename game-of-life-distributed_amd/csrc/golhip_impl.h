@@ -19,6 +19,7 @@
 //   golhip_flips.cpp    flip lists and the flip stream (K5, K5r; a group of strips: K5 + gather)
 //   golhip_view.cpp     live view of one handle and of a group of strips (K7)
 //   golhip_options.cpp  the option table and its consent rules
+//   golhip_ckpt.cpp     checkpoints: shadow copy (K8), drain to a file, verified load
 //
 // Everything here but `struct golhip` lives in namespace gh, whose symbols
 // are hidden: libgolhip.so exports the C-ABI of include/golhip.h alone.
@@ -28,8 +29,10 @@
 
 #include <algorithm>
 #include <atomic>
+#include <condition_variable>
 #include <cstdint>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <vector>
 
@@ -85,6 +88,15 @@ struct Counters {
 // ... and the GOLHIP_FLAG_TIMING sums of the timed spans, by kind (drain_events)
 struct Millis {
     double step = 0, persist = 0, flip = 0, halo = 0, view = 0;
+};
+
+// What a handle keeps of its checkpoint in flight (golhip_ckpt.cpp): whether
+// the shadow has drained to the staging buffers.  Shared with the checkpoint
+// object, which owns everything else and may be freed first.
+struct CkptDrain {
+    std::mutex mu;
+    std::condition_variable cv;
+    bool drained = false;
 };
 
 }  // namespace gh
@@ -185,7 +197,7 @@ struct golhip {
     std::atomic<int64_t> turns{0};
 
     // side-channel scratch
-    unsigned long long *d_scalars = nullptr;  // [0] alive, [1] compaction total, [2] hash
+    unsigned long long *d_scalars = nullptr;  // [0] alive, [1] compaction total, [2] hash, [3] a ring's count; a checkpoint load: [2] alive, [3] hash
     unsigned long long *h_scalars = nullptr;  // pinned mirror
     int64_t alive_turn = -1;                  // turn whose count sits in d_scalars[0]
     gh::DevScratch<unsigned long long> d_blk;
@@ -243,9 +255,13 @@ struct golhip {
     gh::Counters n;
     gh::Millis ms;  // (halo: exchange time on the engine stream)
 
+    std::shared_ptr<gh::CkptDrain> ckpt_drain;  // the last golhip_checkpoint_begin on this handle
+
     std::mutex mu;
 
     int64_t local_words() const { return (int64_t)rows * Ww; }
+    // (K8's 16-byte loads and stores start at these: kHalo * Ww words are whole 16-byte groups)
+    static_assert(golk::kHalo % 4 == 0, "the rows behind the top halo must stay 16-byte aligned");
     uint32_t *cur_rows() const { return buf[cur] + (int64_t)golk::kHalo * Ww; }
     uint32_t *prev_rows() const { return buf[cur ^ 1] + (int64_t)golk::kHalo * Ww; }
     bool torus() const { return nranks == 1 && rows == H; }
@@ -319,7 +335,7 @@ golk::StepArgs step_args(golhip_t h, unsigned long long *alive, bool halo);
 int exchange_rccl(golhip_t h, int depth, hipStream_t st);
 int launch_depth(golhip_t h, int depth, bool count, bool halo);
 int step_checked_locked(golhip_t h, int64_t nturns, int32_t want_flips);
-int group_check(golhip_t *hs, int32_t n);
+int group_check(golhip_t *hs, int32_t n, bool need_board = true);  // need_board: every strip loaded
 int group_step_locked(golhip_t *hs, int32_t n, int64_t nturns, int32_t want_flips, hipEvent_t *keep = nullptr);
 // Halo rows of every strip from its ring neighbours' current boards, x rows
 // each way, by peer copies ordered through the n events `ready`.  relaunch:

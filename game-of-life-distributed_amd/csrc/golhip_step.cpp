@@ -496,11 +496,11 @@ int step_checked_locked(golhip_t h, int64_t nturns, int32_t want_flips) {
 // list of the last turn (golhip_flips, global coordinates, strip order =
 // row-major order of the board).
 // The strips of a group: one board, contiguous from row 0, covering it.
-int group_check(golhip_t *hs, int32_t n) {
+int group_check(golhip_t *hs, int32_t n, bool need_board) {
     if (!hs || n < 1) return fail(GOLHIP_EINVAL, "bad group");
     for (int i = 0; i < n; ++i) {
         if (int rc = check(hs[i])) return rc;
-        if (!hs[i]->loaded) return fail(GOLHIP_EINVAL, "strip %d has no board", i);
+        if (need_board && !hs[i]->loaded) return fail(GOLHIP_EINVAL, "strip %d has no board", i);
         if (hs[i]->W != hs[0]->W || hs[i]->H != hs[0]->H || hs[i]->nranks != 1)
             return fail(GOLHIP_EINVAL, "strip %d does not belong to the group", i);
         const int expect_row0 = i == 0 ? 0 : hs[i - 1]->row0 + hs[i - 1]->rows;

@@ -3,6 +3,7 @@
 //
 //   golrun [-t threads] [-w width] [-h height] [-turns n] [-noVis] [-root dir] [-device n]
 //          [-viewScale n] [-viewEvery n] [-viewDir dir] [-viewStrips]
+//          [-checkpoint path] [-checkpointEvery n] [-resume path]
 //
 // Same flags, defaults and output as main.go: "Threads: / Width: / Height:"
 // lines, then gol.Run on images/<w>x<h>.pgm with an events channel of
@@ -17,6 +18,11 @@
 // the pixels a window would show (gol_host.h RunOptions::view).  On row strips
 // (GOL_STRIPS / GOL_NGPU) a view needs -viewStrips (or GOL_VIEW_STRIPS=1): the
 // frames are then rendered across the strips, the same pixels.
+// -checkpoint <path> with -checkpointEvery <n> (turns; 0 = off, the default)
+// writes a checkpoint of the board to <path> at every turn that is a multiple
+// of n, behind the following turns, and on `q` one of the turn the run stops
+// at; -resume <path> starts from such a file, at its turn, instead of
+// images/<w>x<h>.pgm (gol_host.h RunOptions::checkpoint_path, resume_path).
 // The headless drain loop ends at FinalTurnComplete (main.go:59-66) or when
 // the events channel closes.
 #include <sys/stat.h>
@@ -35,7 +41,8 @@ namespace {
 
 [[noreturn]] void usage(const char *msg) {
     std::fprintf(stderr, "golrun: %s\nusage: golrun [-t threads] [-w width] [-h height] [-turns n] [-noVis] "
-                         "[-root dir] [-device n] [-viewScale n] [-viewEvery n] [-viewDir dir] [-viewStrips]\n", msg);
+                         "[-root dir] [-device n] [-viewScale n] [-viewEvery n] [-viewDir dir] [-viewStrips] "
+                         "[-checkpoint path] [-checkpointEvery n] [-resume path]\n", msg);
     std::exit(2);
 }
 
@@ -94,10 +101,18 @@ int main(int argc, char **argv) {
             view_dir = value();
         } else if (key == "-viewStrips") {
             opt.view_strips = (eq == std::string::npos || val == "true" || val == "1") ? 1 : 0;
+        } else if (key == "-checkpoint") {
+            opt.checkpoint_path = value();
+        } else if (key == "-checkpointEvery") {
+            opt.checkpoint_every = parse_int(value(), "checkpointEvery");
+        } else if (key == "-resume") {
+            opt.resume_path = value();
         } else {
             usage(("flag provided but not defined: " + key).c_str());
         }
     }
+    if (opt.checkpoint_every < 0 || (opt.checkpoint_every > 0 && opt.checkpoint_path.empty()))
+        usage("-checkpointEvery must be >= 0 and needs -checkpoint <path>");
     params.Turns = turns;  // a Go int (64-bit): the reference's 10^10 default passes through
 
     std::printf("Threads: %lld\nWidth: %lld\nHeight: %lld\n", (long long)params.Threads, (long long)params.ImageWidth,

@@ -19,6 +19,7 @@ HEADER = os.path.join(HERE, "..", "..", "include", "golhip.h")
 GOLHIP_OK = 0
 GOLHIP_EINVAL = -1
 GOLHIP_ERANGE = -4
+GOLHIP_ECORRUPT = -6
 FLIPS_XY, FLIPS_INDEX = 0, 1
 FLAG_TIMING = 0x1
 UNIQUE_ID_BYTES = 128
@@ -90,6 +91,23 @@ class View(ctypes.Structure):
         ("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("scale", ctypes.c_int32),
         ("out_w", ctypes.c_int32), ("out_h", ctypes.c_int32), ("format", ctypes.c_int32),
     ]
+
+
+class CkptOpts(ctypes.Structure):
+    """golhip_ckpt_opts_t"""
+    _fields_ = [("chunk_rows", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
+
+
+class CkptInfo(ctypes.Structure):
+    """golhip_ckpt_info_t"""
+    _fields_ = [
+        ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("turn", ctypes.c_int64),
+        ("alive", ctypes.c_uint64), ("hash", ctypes.c_uint64), ("file_bytes", ctypes.c_uint64),
+        ("stall_ms", ctypes.c_double), ("drain_ms", ctypes.c_double), ("write_ms", ctypes.c_double),
+    ]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 _lib = None
@@ -165,6 +183,10 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "golhip_group_view_frame": ([P(H), i32, P(View), ctypes.c_void_p, u64, P(i64)], ctypes.c_int),
         "golhip_group_view_stream": ([P(H), i32, i64, i64, P(View), ctypes.c_void_p, u64, P(u64), P(i64)],
                                      ctypes.c_int),
+        "golhip_checkpoint_begin": ([P(H), i32, ctypes.c_char_p, P(CkptOpts), P(ctypes.c_void_p)], ctypes.c_int),
+        "golhip_checkpoint_wait": ([ctypes.c_void_p, P(CkptInfo)], ctypes.c_int),
+        "golhip_checkpoint_info": ([ctypes.c_char_p, P(CkptInfo)], ctypes.c_int),
+        "golhip_checkpoint_load": ([P(H), i32, ctypes.c_char_p, P(CkptOpts), P(CkptInfo)], ctypes.c_int),
         "golhip_perf": ([H, P(Perf)], ctypes.c_int),
         "golhip_perf_reset": ([H], ctypes.c_int),
         "golhip_persist_trace": ([H, P(u64)], ctypes.c_int),
@@ -633,6 +655,140 @@ def view_frame_np(words: np.ndarray, width: int, height: int, x0: int = 0, y0: i
 
 
 # --------------------------------------------------------------------------
+# checkpoints (golhip_checkpoint_*; the file format is restated in numpy)
+# --------------------------------------------------------------------------
+CKPT_MAGIC = b"GOLCKPT\x01"
+CKPT_HEADER_BYTES = 64
+
+
+def _handles(boards):
+    boards = [boards] if isinstance(boards, Board) else list(boards)
+    return (ctypes.c_void_p * len(boards))(*[b.handle for b in boards]), len(boards)
+
+
+class Checkpoint:
+    """A checkpoint in flight (golhip_checkpoint_begin); wait() joins it."""
+
+    def __init__(self, ck):
+        self._ck = ck
+
+    def wait(self) -> dict:
+        """golhip_checkpoint_wait: the header's fields, file_bytes and the
+        timings stall_ms, drain_ms, write_ms.  Raises GolHipError on a file or
+        device error (the object is freed either way)."""
+        if not self._ck:
+            raise ValueError("checkpoint already waited for")
+        ck, self._ck = self._ck, None
+        info = CkptInfo()
+        _check(load().golhip_checkpoint_wait(ck, ctypes.byref(info)))
+        return info.as_dict()
+
+    def __del__(self):
+        if getattr(self, "_ck", None):
+            try:
+                load().golhip_checkpoint_wait(self._ck, None)
+            except Exception:
+                pass
+            self._ck = None
+
+
+def checkpoint_begin(boards, path: str, chunk_rows: int = 0) -> Checkpoint:
+    """golhip_checkpoint_begin of one whole-torus Board or the strips of
+    group_step: returns at once; the file is complete after .wait()."""
+    arr, n = _handles(boards)
+    ck = ctypes.c_void_p()
+    opts = CkptOpts(chunk_rows)
+    _check(load().golhip_checkpoint_begin(arr, n, os.fsencode(path), ctypes.byref(opts), ctypes.byref(ck)))
+    return Checkpoint(ck)
+
+
+def checkpoint_info(path: str) -> dict:
+    """golhip_checkpoint_info: header fields and file_bytes (no device needed)."""
+    info = CkptInfo()
+    _check(load().golhip_checkpoint_info(os.fsencode(path), ctypes.byref(info)))
+    d = info.as_dict()
+    return {k: d[k] for k in ("width", "height", "turn", "alive", "hash", "file_bytes")}
+
+
+def checkpoint_load(boards, path: str, chunk_rows: int = 0) -> dict:
+    """golhip_checkpoint_load into one Board or a group of strips: board and
+    turn come from the file, verified against its count and digest."""
+    arr, n = _handles(boards)
+    info = CkptInfo()
+    opts = CkptOpts(chunk_rows)
+    _check(load().golhip_checkpoint_load(arr, n, os.fsencode(path), ctypes.byref(opts), ctypes.byref(info)))
+    d = info.as_dict()
+    return {k: d[k] for k in ("width", "height", "turn", "alive", "hash", "file_bytes")}
+
+
+def _splitmix64_np(x: np.ndarray) -> np.ndarray:
+    with np.errstate(over="ignore"):
+        z = x + np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return z ^ (z >> np.uint64(31))
+
+
+def checkpoint_header_np(width: int, height: int, turn: int, alive: int, digest: int) -> bytes:
+    """The 64 header bytes of a checkpoint file (include/golhip.h)."""
+    ww = (width + 31) // 32
+    q = np.zeros(8, dtype="<u8")
+    q[0] = int.from_bytes(CKPT_MAGIC, "little")
+    q[1] = 1 | (CKPT_HEADER_BYTES << 32)
+    q[2] = width | (height << 32)
+    q[3] = turn % (1 << 64)
+    q[4] = alive
+    q[5] = digest
+    q[6] = ww
+    with np.errstate(over="ignore"):
+        q[7] = _splitmix64_np(q[:7] + np.arange(7, dtype=np.uint64)).sum(dtype=np.uint64)
+    return q.tobytes()
+
+
+def checkpoint_write_np(path: str, words: np.ndarray, width: int, height: int, turn: int) -> None:
+    """Writes a checkpoint file from canonical bit words ((height,
+    ceil(width / 32)) uint32, padding bits zero) with numpy alone."""
+    ww = (width + 31) // 32
+    w = np.ascontiguousarray(words, dtype="<u4").reshape(height, ww)
+    alive = int(np.unpackbits(w.view(np.uint8)).sum(dtype=np.int64))
+    with open(path, "wb") as f:
+        f.write(checkpoint_header_np(width, height, turn, alive, board_hash_np(w)))
+        f.write(w.tobytes())
+
+
+def checkpoint_read_np(path: str, verify: bool = True):
+    """(info, words) of a checkpoint file, checked as golhip_checkpoint_load
+    checks it (ValueError names the failed check; verify=False skips the
+    payload's count and digest): info has width, height,
+    turn, alive, hash, file_bytes; words are (height, ceil(width / 32)) uint32."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if len(data) < CKPT_HEADER_BYTES:
+        raise ValueError(f"file size: {len(data)} bytes, less than the 64-byte header")
+    q = np.frombuffer(data[:CKPT_HEADER_BYTES], dtype="<u8")
+    if data[:8] != CKPT_MAGIC:
+        raise ValueError("magic: not a GOLCKPT file")
+    if int(q[1]) != (1 | (CKPT_HEADER_BYTES << 32)):
+        raise ValueError("version")
+    with np.errstate(over="ignore"):
+        if int(_splitmix64_np(q[:7] + np.arange(7, dtype=np.uint64)).sum(dtype=np.uint64)) != int(q[7]):
+            raise ValueError("header check")
+    width, height, ww = int(q[2]) & 0xFFFFFFFF, int(q[2]) >> 32, int(q[6])
+    if width < 1 or height < 1 or ww != (width + 31) // 32:
+        raise ValueError("header check: impossible geometry")
+    if len(data) != CKPT_HEADER_BYTES + 4 * height * ww:
+        raise ValueError(f"file size: {len(data)} bytes, the header's board needs {CKPT_HEADER_BYTES + 4 * height * ww}")
+    words = np.frombuffer(data, dtype="<u4", offset=CKPT_HEADER_BYTES).reshape(height, ww).astype(np.uint32)
+    info = {"width": width, "height": height, "turn": int(q[3].astype(np.int64)), "alive": int(q[4]), "hash": int(q[5]),
+            "file_bytes": len(data)}
+    if verify and int(np.unpackbits(words.view(np.uint8)).sum(dtype=np.int64)) != info["alive"]:
+        raise ValueError("alive count")
+    if verify and board_hash_np(words) != info["hash"]:
+        raise ValueError("digest")
+    return info, words
+
+
+# --------------------------------------------------------------------------
 # host mirror of gol.Run (libgolhost.so, include/golrun.h)
 # --------------------------------------------------------------------------
 HOST_LIB_PATH = os.environ.get("GOLHOST_LIB") or os.path.join(HERE, "libgolhost.so")  # A/B builds
@@ -649,6 +805,13 @@ class RunEvent(ctypes.Structure):
         ("cells_count", ctypes.c_int64), ("cell_x", ctypes.c_int64), ("cell_y", ctypes.c_int64),
         ("alive_len", ctypes.c_int64), ("filename", ctypes.c_char * 256), ("text", ctypes.c_char * 288),
     ]
+
+
+class RunOpts(ctypes.Structure):
+    """golrun_opts_t"""
+    _fields_ = [("view", ctypes.POINTER(View)), ("view_every", ctypes.c_int32), ("reserved0", ctypes.c_int32),
+                ("checkpoint_path", ctypes.c_char_p), ("checkpoint_every", ctypes.c_int64),
+                ("resume_path", ctypes.c_char_p), ("reserved", ctypes.c_int64 * 4)]
 
 
 class DrainStats(ctypes.Structure):
@@ -672,6 +835,8 @@ def load_host(path: str = HOST_LIB_PATH) -> ctypes.CDLL:
         "golrun_last_error": ([], ctypes.c_char_p),
         "golrun_start": ([i64, i64, i64, i64, ctypes.c_char_p, i32, u32, i32, i32, P(ctypes.c_void_p)], ctypes.c_int),
         "golrun_start_view": ([i64, i64, i64, i64, ctypes.c_char_p, i32, u32, i32, i32, P(View), i32,
+                               P(ctypes.c_void_p)], ctypes.c_int),
+        "golrun_start_opts": ([i64, i64, i64, i64, ctypes.c_char_p, i32, u32, i32, i32, P(RunOpts),
                                P(ctypes.c_void_p)], ctypes.c_int),
         "golrun_view_frame": ([ctypes.c_void_p, ctypes.c_void_p, u64, P(i64)], ctypes.c_int),
         "golrun_event_string": ([P(RunEvent), ctypes.c_char_p, u64], ctypes.c_int),
@@ -697,21 +862,36 @@ class Run:
 
     def __init__(self, turns: int, threads: int, width: int, height: int, root: str, *, device: int = 0,
                  keys: bool = False, quirks: bool = False, cell_events: bool = True, turn_events: bool = True,
-                 events_cap: int = 0, ticker_ms: int = 0, view: dict | None = None):
+                 events_cap: int = 0, ticker_ms: int = 0, view: dict | None = None, checkpoint: dict | None = None,
+                 resume: str | None = None):
         """view: the live view (golrun_start_view), dict(scale=..., every=1,
         x0=0, y0=0, out_w=None, out_h=None, fmt=VIEW_ARGB, strips=False);
         missing out_w / out_h are the largest that fit.  Run.view_frame()
         fetches frames.  strips=True lets a run on row strips (GOL_STRIPS /
-        GOL_NGPU) render its view across them; without it such a run is refused."""
+        GOL_NGPU) render its view across them; without it such a run is refused.
+        checkpoint: dict(path=..., every=0): a checkpoint file at every turn
+        that is a multiple of `every`, and on `q` one of the turn the run stops
+        at.  resume: a checkpoint file the run starts from, at its turn
+        (golrun_start_opts)."""
         lib = load_host()
         flags = (FLAG_KEYS if keys else 0) | (FLAG_REF_QUIRKS if quirks else 0) | \
             (0 if cell_events else FLAG_NO_CELL_EVENTS) | (0 if turn_events else FLAG_NO_TURN_EVENTS)
         h = ctypes.c_void_p()
         self._view = None
-        if view is None:
+        if checkpoint is not None and (set(checkpoint) - {"path", "every"} or "path" not in checkpoint):
+            raise ValueError("checkpoint needs path (and every)")
+        if view is None and checkpoint is None and resume is None:
             rc = lib.golrun_start(turns, threads, width, height, root.encode(), device, flags, events_cap, ticker_ms,
                                   ctypes.byref(h))
         else:
+            ro = RunOpts()
+            ro.view_every = 1
+            if checkpoint is not None:
+                ro.checkpoint_path = os.fsencode(checkpoint["path"])
+                ro.checkpoint_every = int(checkpoint.get("every", 0))
+            if resume is not None:
+                ro.resume_path = os.fsencode(resume)
+        if view is not None:
             unknown = set(view) - {"scale", "every", "x0", "y0", "out_w", "out_h", "fmt", "strips"}
             if unknown or "scale" not in view:
                 raise ValueError(f"view needs scale; unknown keys {sorted(unknown)}")
@@ -721,8 +901,16 @@ class Run:
                               height // max(s, 1) if oh is None else oh, view.get("fmt", VIEW_ARGB))
             if view.get("strips"):
                 flags |= FLAG_VIEW_STRIPS
-            rc = lib.golrun_start_view(turns, threads, width, height, root.encode(), device, flags, events_cap,
-                                       ticker_ms, ctypes.byref(self._view), int(view.get("every", 1)), ctypes.byref(h))
+            if checkpoint is None and resume is None:
+                rc = lib.golrun_start_view(turns, threads, width, height, root.encode(), device, flags, events_cap,
+                                           ticker_ms, ctypes.byref(self._view), int(view.get("every", 1)),
+                                           ctypes.byref(h))
+            else:
+                ro.view = ctypes.pointer(self._view)
+                ro.view_every = int(view.get("every", 1))
+        if checkpoint is not None or resume is not None:
+            rc = lib.golrun_start_opts(turns, threads, width, height, root.encode(), device, flags, events_cap,
+                                       ticker_ms, ctypes.byref(ro), ctypes.byref(h))
         if rc != 0:
             raise GolHipError(rc, lib.golrun_last_error().decode())
         self._h = h

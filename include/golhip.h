@@ -44,6 +44,7 @@ extern "C" {
 #define GOLHIP_ENOMEM (-3)  /* device or host allocation failed               */
 #define GOLHIP_ERANGE (-4)  /* caller buffer too small (required size is set) */
 #define GOLHIP_ERCCL (-5)   /* RCCL error                                     */
+#define GOLHIP_ECORRUPT (-6) /* checkpoint file damaged: header check, size, digest or count */
 
 /* golhip_create flags */
 #define GOLHIP_FLAG_TIMING 0x1u /* time every step kernel with HIP events     */
@@ -407,6 +408,74 @@ int golhip_group_view_frame(golhip_t *hs, int32_t n, const golhip_view_t *v, voi
  * Results as golhip_view_stream (GOLHIP_ERANGE with nothing advanced). */
 int golhip_group_view_stream(golhip_t *hs, int32_t n, int64_t nturns, int64_t every, const golhip_view_t *v, void *out,
                              uint64_t cap_frames, uint64_t *frames, int64_t *turns_done);
+
+/* ---- checkpoint and resume -------------------------------------------- */
+/* Fault tolerance as checkpoint and restart (the reference README's third
+ * extension, and its "a new controller should be able to take over" after
+ * `q`): a GPU fault or a pre-empted job ends the process, so the state that
+ * survives is a file, and a new process resumes from it at its turn.
+ *
+ * The file, little-endian, exactly 64 + 4 * height * Ww bytes, Ww =
+ * ceil(width / 32): eight uint64 -- the bytes "GOLCKPT" 0x01; version 1 | 64
+ * << 32; width | height << 32; the turn; the board's alive cells; its
+ * golhip_board_hash; Ww; and the sum over i = 0..6 of splitmix64(q_i + i) --
+ * then the board's bit words as golhip_snapshot_bits gives them, row-major
+ * over the whole torus.  It does not depend on the word layout, the strips or
+ * the devices: one board at one turn gives one file.
+ *
+ * hs, n: one whole-torus handle (n = 1) or the group golhip_group_step takes
+ * (strips contiguous from row 0, covering the board).  Not for handles of an
+ * RCCL ring (GOLHIP_EINVAL). */
+typedef struct golhip_ckpt golhip_ckpt;
+typedef struct golhip_ckpt_opts {
+    int32_t chunk_rows;   /* rows a staging buffer holds; 0 = automatic (16 MiB)  */
+    int32_t reserved[3];  /* zero                                                 */
+} golhip_ckpt_opts_t;
+typedef struct golhip_ckpt_info {
+    int32_t width, height;
+    int64_t turn;
+    uint64_t alive, hash, file_bytes;
+    double stall_ms;   /* device time of the checkpoint kernels (sum over strips; HIP events) */
+    double drain_ms;   /* from the first copy to the last byte in the staging buffers          */
+    double write_ms;   /* from opening <path>.tmp to the rename                               */
+} golhip_ckpt_info_t;
+/* Starts a checkpoint of the board at its current turn (every strip at the
+ * same turn, else GOLHIP_EINVAL) and returns once it is enqueued, without
+ * synchronising the host.  Each handle's stream gets one kernel behind the
+ * turns already enqueued: it reads the rows in the layout they are stepped in,
+ * writes nothing to them, and stores the canonical words, their count and
+ * their digest to a shadow buffer that the checkpoint object owns.  Turns
+ * enqueued afterwards run on at once.  Behind the kernel a side stream of the
+ * object copies the shadow to the host in chunks of chunk_rows rows through
+ * two page-locked buffers, and a writer thread writes each chunk at its place
+ * in <path>.tmp, then the header, then fsyncs and renames it over <path>: an
+ * existing <path> stays whole until that moment, whatever fails.  A handle's
+ * mutex is held for its own enqueue only.  A second begin on a handle first
+ * waits until the earlier checkpoint of that handle has left the device (it
+ * neither joins nor frees it).  golhip_destroy of the handles is legal as soon
+ * as begin has returned.  opts nullable. */
+int golhip_checkpoint_begin(golhip_t *hs, int32_t n, const char *path, const golhip_ckpt_opts_t *opts,
+                            golhip_ckpt **out);
+/* Joins the writer, reports (info nullable) and frees ck.  File errors
+ * (GOLHIP_EINVAL: <path>.tmp cannot be created, written or renamed) and device
+ * errors are reported here; no <path>.tmp is left behind either outcome. */
+int golhip_checkpoint_wait(golhip_ckpt *ck, golhip_ckpt_info_t *info);
+/* Header and size of a checkpoint file (timings zero); needs no device.
+ * GOLHIP_ECORRUPT, the message naming the check, for a wrong magic, version,
+ * header check or file size; GOLHIP_EINVAL if it cannot be opened. */
+int golhip_checkpoint_info(const char *path, golhip_ckpt_info_t *info);
+/* Fills each handle's rows [row0, row0 + rows) from the file, chunk by chunk
+ * through page-locked buffers (the file is never held whole), in the layout
+ * the handle steps in, and sets every handle's turn to the file's: the one way
+ * to a turn other than 0.  Counts and flip lists kept by the handles are
+ * dropped as golhip_load_bits drops them.  The kernel that stores the rows
+ * clears the bits of columns >= width and sums count and digest of what it
+ * stored; the strips' sums must equal the header's.  A file of another width
+ * or height: GOLHIP_EINVAL.  A bad magic, version, header check, file size,
+ * count or digest: GOLHIP_ECORRUPT, the message naming the check.  After an
+ * error the handles' boards are unspecified.  opts, info nullable. */
+int golhip_checkpoint_load(golhip_t *hs, int32_t n, const char *path, const golhip_ckpt_opts_t *opts,
+                           golhip_ckpt_info_t *info);
 
 /* ---- measurement ------------------------------------------------------ */
 int golhip_perf(golhip_t h, golhip_perf_t *out);

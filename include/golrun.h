@@ -74,6 +74,31 @@ int golrun_start(int64_t turns, int64_t threads, int64_t width, int64_t height, 
 int golrun_start_view(int64_t turns, int64_t threads, int64_t width, int64_t height, const char *root,
                       int32_t device, uint32_t flags, int32_t events_cap, int32_t ticker_ms,
                       const golhip_view_t *view, int32_t every, golrun_t *out);
+/* golrun_start_view with checkpointing and resume (gol_host.h RunOptions):
+ * view nullable (view_every is then ignored).
+ * checkpoint_path (nullable): a checkpoint file (golhip.h) is written there at
+ * every turn that is a multiple of checkpoint_every (0: none) behind the
+ * following turns, the last one before FinalTurnComplete; on `q` one of the
+ * turn the run stops at, complete before StateChange{Quitting}: the state a
+ * new controller takes over.
+ * resume_path (nullable): board and turn T come from that checkpoint instead
+ * of images/<W>x<H>.pgm.  Its size must equal width x height and T <= turns,
+ * else the run fails where the image read fails (golrun_wait has the message,
+ * no event is sent).  The initial CellFlipped events are the alive cells of
+ * that board at turn T; TurnComplete continues at T + 1; T == turns goes
+ * straight to FinalTurnComplete. */
+typedef struct golrun_opts {
+    const golhip_view_t *view;
+    int32_t view_every;
+    int32_t reserved0;
+    const char *checkpoint_path;
+    int64_t checkpoint_every;
+    const char *resume_path;
+    int64_t reserved[4];    /* zero */
+} golrun_opts_t;
+int golrun_start_opts(int64_t turns, int64_t threads, int64_t width, int64_t height, const char *root,
+                      int32_t device, uint32_t flags, int32_t events_cap, int32_t ticker_ms,
+                      const golrun_opts_t *opts, golrun_t *out);
 /* Copy of the newest published frame and the turn its pixels show.  After
  * TurnComplete{t} of a run with every = 1 that turn is >= t; while paused it
  * stays at the paused turn; after FinalTurnComplete it is the final board.

@@ -32,6 +32,16 @@ package gol
 // =none also the per-turn ones, which lets the engine fuse 256 turns a call.
 // Every engine call holds mu, so the ticker, the keys and a pause act between
 // batches, at a turn boundary.
+//
+// Checkpoint and resume (Params is the reference's and has no room for them,
+// so they come from the environment, like GOL_STRIPS): GOL_CHECKPOINT=<path>
+// with GOL_CHECKPOINT_EVERY=<n> writes a checkpoint file at every turn that is
+// a multiple of n (an engine call ends there; the file drains behind the
+// following turns) and, on q, one of the turn the run stops at, complete
+// before StateChange{Quitting}: the state a new controller takes over (README
+// stage 2, step 4).  GOL_RESUME=<path> starts from such a file instead of the
+// image: the initial CellFlipped events are its board's alive cells at its
+// turn T, TurnComplete continues at T + 1.
 
 import (
 	"fmt"
@@ -57,6 +67,10 @@ var (
 	refQuirks  = os.Getenv("GOL_REF_QUIRKS") == "1"
 	cellEvents = os.Getenv("GOLHIP_EVENTS") != "turns" && os.Getenv("GOLHIP_EVENTS") != "none"
 	turnEvents = os.Getenv("GOLHIP_EVENTS") != "none"
+
+	checkpointPath  = os.Getenv("GOL_CHECKPOINT")
+	checkpointEvery = envInt("GOL_CHECKPOINT_EVERY", 0) // turns; 0: only on q
+	resumePath      = os.Getenv("GOL_RESUME")
 )
 
 const (
@@ -109,21 +123,26 @@ func snapshotRaster(eng *engine) []byte {
 
 func distributor(p Params, c distributorChannels) {
 	name := strconv.Itoa(p.ImageWidth) + "x" + strconv.Itoa(p.ImageHeight)
-	c.ioFilename <- name
-	c.ioCommand <- ioInput
-	cells := make([]byte, p.ImageWidth*p.ImageHeight) // row-major, H rows of W bytes
-	for i := range cells {
-		cells[i] = <-c.ioInput
+	var eng *engine
+	turn := 0 // completed turns; written by this goroutine under mu
+	if resumePath != "" {
+		eng, turn = resumeEngine(p, resumePath) // board and turn of the checkpoint
+	} else {
+		c.ioFilename <- name
+		c.ioCommand <- ioInput
+		cells := make([]byte, p.ImageWidth*p.ImageHeight) // row-major, H rows of W bytes
+		for i := range cells {
+			cells[i] = <-c.ioInput
+		}
+		eng = newEngine(p, cells)
 	}
-	eng := newEngine(p, cells)
 	defer eng.close()
 
-	for _, cell := range eng.aliveCells() { // :72-80
-		c.events <- CellFlipped{CompletedTurns: 0, Cell: flipped(cell.X, cell.Y)}
+	for _, cell := range eng.aliveCells() { // :72-80 (a resumed run: the checkpoint's board, at its turn)
+		c.events <- CellFlipped{CompletedTurns: turn, Cell: flipped(cell.X, cell.Y)}
 	}
 
 	var mu sync.Mutex // held by every engine call and by a pause
-	turn := 0         // completed turns; written by this goroutine under mu
 	finished := make(chan struct{})
 	quit := make(chan struct{}) // closed by 'q'
 	var helpers sync.WaitGroup
@@ -163,6 +182,12 @@ func distributor(p Params, c distributorChannels) {
 					t := turn
 					fname := name + "x" + strconv.Itoa(t)
 					writeImage(c, fname, snapshotRaster(eng))
+					// with checkpointing on, quit is closed under mu: the turn loop stops at the
+					// snapshot's turn, the turn of the take-over checkpoint
+					early := k == 'q' && !refQuirks && checkpointPath != ""
+					if early {
+						close(quit)
+					}
 					mu.Unlock()
 					if k == 'q' {
 						c.ioCommand <- ioCheckIdle
@@ -173,7 +198,9 @@ func distributor(p Params, c distributorChannels) {
 						if refQuirks {
 							os.Exit(0) // :261
 						}
-						close(quit)
+						if !early {
+							close(quit)
+						}
 						return
 					}
 				case 'p':
@@ -218,10 +245,17 @@ func distributor(p Params, c distributorChannels) {
 		if want > batch {
 			want = batch
 		}
+		if checkpointEvery > 0 && want > checkpointEvery-turn%checkpointEvery {
+			want = checkpointEvery - turn%checkpointEvery // an engine call ends on every checkpoint turn
+		}
 		var done int
 		var counts []uint64
 		var idx []uint32
 		mu.Lock()
+		if stopped() { // q took its snapshot while this goroutine waited for mu
+			mu.Unlock()
+			break
+		}
 		if cellEvents {
 			done, counts, idx = eng.flipStream(want)
 		} else {
@@ -230,7 +264,14 @@ func distributor(p Params, c distributorChannels) {
 		}
 		first := turn
 		turn += done
+		due := checkpointPath != "" && checkpointEvery > 0 && done > 0 && turn%checkpointEvery == 0
 		mu.Unlock()
+		if due {
+			eng.checkpointWait() // the previous one's writer (fsync, rename), off mu: the helpers are not held up
+			mu.Lock()
+			eng.checkpointBegin(checkpointPath, turn) // only the enqueue
+			mu.Unlock()
+		}
 		// the batch's events, turn by turn: CellFlipped before TurnComplete (event.go:57)
 		off := 0
 		for i := 0; i < done; i++ {
@@ -251,11 +292,18 @@ func distributor(p Params, c distributorChannels) {
 	close(finished)
 	helpers.Wait()
 	if stopped() { // 'q' already wrote its snapshot and sent ImageOutputComplete (:244-261)
+		if checkpointPath != "" { // the state a new controller takes over
+			if eng.ckptTurn != turn {
+				eng.checkpointBegin(checkpointPath, turn)
+			}
+			eng.checkpointWait()
+		}
 		c.events <- StateChange{CompletedTurns: turn, NewState: Quitting}
 		close(c.events)
 		return
 	}
 
+	eng.checkpointWait()      // the last periodic checkpoint is on disk before FinalTurnComplete
 	alive := eng.aliveCells() // :180
 	fname := name + "x" + strconv.Itoa(p.Turns)
 	writeImage(c, fname, eng.snapshot()) // :182-191

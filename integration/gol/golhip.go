@@ -70,6 +70,16 @@ package gol
 //                                       void *out, uint64_t cap, uint64_t *frames, int64_t *done) {
 //     return gh_wrap(golhip_group_view_stream(hs, n, t, every, v, out, cap, frames, done));
 // }
+// static gh_status gh_checkpoint_begin(golhip_t *hs, int32_t n, const char *path, golhip_ckpt **out) {
+//     return gh_wrap(golhip_checkpoint_begin(hs, n, path, NULL, out));
+// }
+// static gh_status gh_checkpoint_wait(golhip_ckpt *ck) { return gh_wrap(golhip_checkpoint_wait(ck, NULL)); }
+// static gh_status gh_checkpoint_info(const char *path, golhip_ckpt_info_t *info) {
+//     return gh_wrap(golhip_checkpoint_info(path, info));
+// }
+// static gh_status gh_checkpoint_load(golhip_t *hs, int32_t n, const char *path) {
+//     return gh_wrap(golhip_checkpoint_load(hs, n, path, NULL, NULL));
+// }
 import "C"
 
 import (
@@ -99,6 +109,9 @@ type engine struct {
 
 	framesP unsafe.Pointer // golhip_host_alloc buffer of view frames (ARGB8888)
 	frames  []uint32       // a Go view of it
+
+	ckpt     *C.golhip_ckpt // the checkpoint in flight (at most one)
+	ckptTurn int            // turn of the last checkpoint begun (-1: none)
 }
 
 // check turns a libgolhip status into the reference's fail-fast behaviour
@@ -120,7 +133,60 @@ func envInt(name string, dflt int) int {
 // newEngine replaces the world allocation and fill of distributor.go:66-80:
 // cells is the raster the io goroutine sent, row-major, alive <=> 255.
 func newEngine(p Params, cells []byte) *engine {
-	e := &engine{width: p.ImageWidth, height: p.ImageHeight}
+	e := createEngine(p)
+	for i, h := range e.hs {
+		check(C.gh_load_bytes(h, (*C.uint8_t)(unsafe.Pointer(&cells[e.row0[i]*e.width]))))
+	}
+	return e
+}
+
+// resumeEngine is newEngine from a checkpoint file (golhip_checkpoint_load)
+// instead of the io goroutine's raster: the board and the turn it is at.  It
+// panics where the io goroutine panics on a bad image: another size than
+// Params, a turn past Params.Turns, a damaged file.
+func resumeEngine(p Params, path string) (*engine, int) {
+	cpath := C.CString(path)
+	defer C.free(unsafe.Pointer(cpath))
+	var info C.golhip_ckpt_info_t
+	check(C.gh_checkpoint_info(cpath, &info))
+	if int(info.width) != p.ImageWidth {
+		panic("Incorrect width")
+	}
+	if int(info.height) != p.ImageHeight {
+		panic("Incorrect height")
+	}
+	if int(info.turn) > p.Turns {
+		panic("checkpoint " + path + " is at turn " + strconv.Itoa(int(info.turn)) + ", past the run's turns")
+	}
+	e := createEngine(p)
+	check(C.gh_checkpoint_load((*C.golhip_t)(unsafe.Pointer(&e.hs[0])), C.int32_t(len(e.hs)), cpath))
+	return e, int(info.turn)
+}
+
+// checkpointBegin starts a checkpoint of the board at its current turn
+// (golhip_checkpoint_begin: one kernel a strip behind the turns enqueued; the
+// file drains behind the following turns), after waiting for the previous one.
+func (e *engine) checkpointBegin(path string, turn int) {
+	e.checkpointWait()
+	cpath := C.CString(path)
+	defer C.free(unsafe.Pointer(cpath))
+	check(C.gh_checkpoint_begin((*C.golhip_t)(unsafe.Pointer(&e.hs[0])), C.int32_t(len(e.hs)), cpath, &e.ckpt))
+	e.ckptTurn = turn
+}
+
+// checkpointWait joins the checkpoint in flight: its file is complete, or the
+// run panics with the file error.
+func (e *engine) checkpointWait() {
+	if e.ckpt != nil {
+		ck := e.ckpt
+		e.ckpt = nil
+		check(C.gh_checkpoint_wait(ck))
+	}
+}
+
+// createEngine makes the handles of newEngine / resumeEngine (no board yet).
+func createEngine(p Params) *engine {
+	e := &engine{width: p.ImageWidth, height: p.ImageHeight, ckptTurn: -1}
 	ngpu := envInt("GOL_NGPU", 1)
 	n := envInt("GOL_STRIPS", 0)
 	if n <= 0 {
@@ -156,13 +222,14 @@ func newEngine(p Params, cells []byte) *engine {
 			e.row0 = append(e.row0, r0)
 		}
 	}
-	for i, h := range e.hs {
-		check(C.gh_load_bytes(h, (*C.uint8_t)(unsafe.Pointer(&cells[e.row0[i]*e.width]))))
-	}
 	return e
 }
 
 func (e *engine) close() {
+	if e.ckpt != nil {
+		C.golhip_checkpoint_wait(e.ckpt, nil)
+		e.ckpt = nil
+	}
 	if e.flipsP != nil {
 		C.golhip_host_free(e.flipsP)
 		e.flipsP = nil
