@@ -12,7 +12,9 @@
 //     cleared, with the count and digest of what it stored.
 // A lane owns 16 bytes: one 16-byte load and one 16-byte store per four words;
 // the at most three words behind the last whole group go one at a time.  Both
-// buffers are 16-byte aligned (the callers pass whole strips).  Its own
+// buffers are 16-byte aligned (the callers pass whole strips).  Every tail,
+// the padding mask at each lane position, a second block and a second lap of
+// the grid: tests/test_gpu_ckpt_edges.py (it restates ckpt_blocks()).  Its own
 // translation unit, behind gol_kernels.o on the link line: the step kernels'
 // code object does not move.
 #include <hip/hip_runtime.h>

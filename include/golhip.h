@@ -424,8 +424,11 @@ int golhip_group_view_stream(golhip_t *hs, int32_t n, int64_t nturns, int64_t ev
  * the devices: one board at one turn gives one file.
  *
  * hs, n: one whole-torus handle (n = 1) or the group golhip_group_step takes
- * (strips contiguous from row 0, covering the board).  Not for handles of an
- * RCCL ring (GOLHIP_EINVAL). */
+ * (strips contiguous from row 0, covering the board).  golhip_checkpoint_begin
+ * is not for handles of an RCCL ring (GOLHIP_EINVAL, one-rank rings included).
+ * golhip_checkpoint_load takes the handle of a one-rank ring as the whole torus
+ * it is (the turns after it are planned as before the load) and
+ * refuses a rank of a larger ring: it is no group (GOLHIP_EINVAL). */
 typedef struct golhip_ckpt golhip_ckpt;
 typedef struct golhip_ckpt_opts {
     int32_t chunk_rows;   /* rows a staging buffer holds; 0 = automatic (16 MiB)  */
