@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "gol_limits.h"
+#include "gol_pad_plan.h"
 
 namespace golk {
 
@@ -323,6 +324,25 @@ hipError_t launch_ckpt(const uint32_t *rows, uint32_t *shadow, int64_t nwords, i
 // columns >= W cleared; sums as above, of the words stored.
 hipError_t launch_ckpt_load(const uint32_t *stage, uint32_t *rows, int64_t nwords, int64_t word0, int W, int Ww, int il,
                             unsigned long long *sums, hipStream_t s);
+
+// gol_pad.hip: the padded torus of a board whose width is no multiple of 32
+// (gol_pad_plan.h).  `canon`: the board's rows, Ww = ceil(W / 32) canonical
+// words each; `wide`: the Wp-column board's rows, Wwp = Wp / 32 words each, in
+// layout il (0, 2: Wwp even, 4: Wwp % 4 == 0; rows 8- / 16-byte aligned).
+struct PadArgs {
+    uint32_t *canon;
+    uint32_t *wide;
+    int rows, Ww, Wwp;
+    PadPlan plan;
+    unsigned long long *alive;  // launch_unpad, nullable: += popcount of the real columns
+};
+// canon -> wide, ghost columns included (canon is read only).
+hipError_t launch_pad(const PadArgs &a, int il, hipStream_t s);
+// The ghost columns of `wide` from its real columns (canon unused): only the
+// chunks from the one that holds column W to the row's end are written.
+hipError_t launch_seam(const PadArgs &a, int il, hipStream_t s);
+// wide -> canon: the real columns, the last word's padding bits cleared.
+hipError_t launch_unpad(const PadArgs &a, int il, hipStream_t s);
 
 // "NAME=value ..." of the build's tuning macros (golhip_build_info).
 const char *build_info();

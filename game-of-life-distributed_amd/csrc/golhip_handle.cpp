@@ -141,8 +141,13 @@ static int check_persist(golhip_t h) {
 // After the stream has synchronised: the K1w spin-bound flag of the launches
 // it ran (reported by the call that ran them, then cleared).
 int take_skew_err(golhip_t h) {
-    if (h->skew_err && *h->skew_err) {
-        *h->skew_err = 0;
+    bool err = h->skew_err && *h->skew_err;
+    if (err) *h->skew_err = 0;
+    if (golhip *w = h->wide; w && w->skew_err && *w->skew_err) {  // the padded torus' launches (golhip_pad.cpp)
+        *w->skew_err = 0;
+        err = true;
+    }
+    if (err) {
         return fail(GOLHIP_EHIP, "skewed-band step kernel: a band waited past its spin bound for the band below "
                                  "(board state is undefined)");
     }
@@ -338,6 +343,7 @@ int golhip_destroy(golhip_t h) {
     int rc = GOLHIP_OK;
     HIP_RC(hipSetDevice(h->device));
     if (h->stream) HIP_RC(hipStreamSynchronize(h->stream));
+    if (int prc = pad_destroy(h); prc && rc == GOLHIP_OK) rc = prc;
     for (auto &p : h->ev_pending) {
         HIP_RC(hipEventDestroy(p.e0));
         HIP_RC(hipEventDestroy(p.e1));
@@ -381,6 +387,7 @@ int golhip_set_stream(golhip_t h, void *s) {
     if (h->own_stream) HIP_OR_FAIL(hipStreamDestroy(h->stream));
     h->own_stream = false;
     h->stream = (hipStream_t)s;
+    if (h->wide) h->wide->stream = h->stream;
     return GOLHIP_OK;
 }
 
@@ -553,7 +560,12 @@ int golhip_perf(golhip_t h, golhip_perf_t *out) {
     if (int rc = set_dev(h)) return rc;
     if (int rc = sync_stream(h)) return rc;
     if (int rc = drain_events(h)) return rc;
-    memset(out, 0, sizeof *out);  // (reserved1, reserved2: retired kernel families (round 5), kept for the ABI)
+    if (h->wide) {  // the padded torus' timed launches are this handle's step launches
+        if (int rc = drain_events(h->wide)) return rc;
+        h->ms.step += h->wide->ms.step;
+        h->wide->ms = Millis{};
+    }
+    memset(out, 0, sizeof *out);  // (reserved2: a retired kernel family (round 5), kept for the ABI)
     const Counters &n = h->n;
     out->turns = h->turns;
     out->step_launches = n.step_launches;
@@ -584,6 +596,7 @@ int golhip_perf(golhip_t h, golhip_perf_t *out) {
     out->flip_resident_launches = n.flip_resident;
     out->view_frames = n.view_frames;
     out->view_kernel_ms = h->ms.view;
+    out->pad_launches = n.pad_launches;
     out->words_per_lane = h->W % 32 == 0 ? wpl_for(h) : 0;
     out->persist_depth = h->W % 32 == 0 ? persist_depth_for(h, wpl_for(h)) : 0;
     return GOLHIP_OK;
@@ -618,6 +631,10 @@ int golhip_perf_reset(golhip_t h) {
     std::lock_guard<std::mutex> g(h->mu);
     if (int rc = set_dev(h)) return rc;
     if (int rc = drain_events(h)) return rc;
+    if (h->wide) {
+        if (int rc = drain_events(h->wide)) return rc;
+        h->wide->ms = Millis{};
+    }
     // (turns, persist_fallbacks, flip_fallbacks and the plan caches stay)
     h->n = Counters{};
     h->ms = Millis{};

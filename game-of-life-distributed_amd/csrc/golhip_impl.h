@@ -20,6 +20,7 @@
 //   golhip_view.cpp     live view of one handle and of a group of strips (K7)
 //   golhip_options.cpp  the option table and its consent rules
 //   golhip_ckpt.cpp     checkpoints: shadow copy (K8), drain to a file, verified load
+//   golhip_pad.cpp      the padded torus: widths that are no multiple of 32 on the fast kernels
 //
 // Everything here but `struct golhip` lives in namespace gh, whose symbols
 // are hidden: libgolhip.so exports the C-ABI of include/golhip.h alone.
@@ -84,6 +85,7 @@ struct Counters {
     int64_t flip_launches = 0, flip_entries = 0;
     int64_t flip_resident = 0;  // K5r launches (flip_overlap 2)
     int64_t view_frames = 0;    // frames rendered (K7)
+    int64_t pad_launches = 0;   // seam refreshes of the padded torus, one per wide launch
 };
 // ... and the GOLHIP_FLAG_TIMING sums of the timed spans, by kind (drain_events)
 struct Millis {
@@ -167,6 +169,7 @@ struct golhip {
     gh::DevScratch<uint32_t> lds_edge;  // K1r edge rows (golk::lds_band_edge_words)
     int persistent = -1;        // option "persistent": K1p for long torus runs (1 on, 0 off, -1 auto)
     int wpl_opt = 0;            // option "wpl": words per lane (0 = auto, 1, 2, 4)
+    bool no_quads = false;      // the automatic words per lane are 1 or 2 (the wide board of a padded torus)
     int persist_depth = 0;      // option "persist_depth" (0: tb_depth)
     int persist_waves = 0;      // option "persist_waves": waves per workgroup (0: default)
     int paired_bands = 1;       // option "paired_bands": SIMD mates share two bands from both ends (persistent)
@@ -257,6 +260,14 @@ struct golhip {
 
     std::shared_ptr<gh::CkptDrain> ckpt_drain;  // the last golhip_checkpoint_begin on this handle
 
+    // the padded torus (golhip_pad.cpp): a whole torus with W % 32 != 0 and no
+    // communicator steps as the Wp x H torus `wide` (same device and stream,
+    // per-launch kernels only), created at its first such step and destroyed
+    // with this handle.  The canonical board here is whole between calls.
+    golhip *wide = nullptr;
+    int pad_mode = -1;        // golhip_set_pad_step: -1 the measured rule, 0 never, 1 always
+    bool pad_nomem = false;   // the wide board could not be allocated: the rule stays on K1g
+
     std::mutex mu;
 
     int64_t local_words() const { return (int64_t)rows * Ww; }
@@ -346,6 +357,15 @@ int group_exchange(golhip_t *hs, int32_t n, int x, hipEvent_t *ready, bool relau
 
 // ---- golhip_flips.cpp -------------------------------------------------------
 int start_flips(golhip_t h);
+
+// ---- golhip_pad.cpp ---------------------------------------------------------
+bool pad_applies(golhip_t h);                // a whole torus, W % 32 != 0, no communicator
+bool pad_wanted(golhip_t h, int64_t nturns);  // this step of nturns turns takes the padded path
+// nturns >= 1 turns of h on its wide board: pad, seam + launch for each launch
+// of the wide board's plan, unpad with the count.  *ran false (rc 0): the wide
+// board could not be had and the rule falls back to K1g.
+int pad_step(golhip_t h, int64_t nturns, bool *ran);
+int pad_destroy(golhip_t h);                 // the wide board, if any (golhip_destroy)
 
 // ---- golhip_options.cpp -----------------------------------------------------
 bool tuning_env();      // GOLHIP_TUNING=1 (or GOLHIP_MEASUREMENT=1)

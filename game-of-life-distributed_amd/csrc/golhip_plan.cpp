@@ -156,7 +156,9 @@ static int wpl_per_launch(golhip_t h) {
             return (double)h->Ww / (golk::tb_tiles(h->Ww, wpl) * 62.0 * wpl) / slots_per_word(wpl) * deep;
         };
         const int two = rate(2) >= rate(1) ? 2 : 1;
-        return (h->W % 128 == 0 && rate(4) > 1.03 * rate(two)) ? 4 : two;
+        // (the wide board of a padded torus pays a seam refresh a launch and
+        // takes quads, at most 9 turns a launch, only when asked to: golhip_pad.cpp)
+        return (!h->no_quads && h->W % 128 == 0 && rate(4) > 1.03 * rate(two)) ? 4 : two;
     }
 }
 

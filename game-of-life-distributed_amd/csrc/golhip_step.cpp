@@ -395,6 +395,13 @@ static int step_locked(golhip_t h, int64_t nturns, int32_t want_flips) {
     int64_t left = nturns;
     const int64_t tail = want_flips ? 1 : 0;
     const bool halo = h->halo_mode();
+    if (pad_wanted(h, left - tail)) {
+        // a width that is no multiple of 32 on the fast kernels (golhip_pad.cpp);
+        // the last turn of a want_flips step runs on K1g below, as ever
+        bool ran = false;
+        if (int rc = pad_step(h, left - tail, &ran)) return rc;
+        if (ran) left = tail;
+    }
     if (!halo) {
         // resident launches while they apply (more than one only past
         // golk::kResidentMaxTurns turns), then per-launch kernels for the rest

@@ -58,7 +58,7 @@ class Perf(ctypes.Structure):
         ("flip_fallbacks", ctypes.c_int64),
         ("persist_depth", ctypes.c_int32),
         ("reserved0", ctypes.c_int32),
-        ("reserved1", ctypes.c_int64),
+        ("pad_launches", ctypes.c_int64),
         ("skew_launches", ctypes.c_int64),
         ("halo_exchanges", ctypes.c_int64),
         ("halo_ms", ctypes.c_double),
@@ -152,6 +152,7 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "golhip_set_tb_depth": ([H, i32], ctypes.c_int),
         "golhip_set_rows_per_wave": ([H, i32], ctypes.c_int),
         "golhip_set_option": ([H, ctypes.c_char_p, i64], ctypes.c_int),
+        "golhip_set_pad_step": ([H, i32], ctypes.c_int),
         "golhip_comm_unique_id": ([ctypes.c_char_p], ctypes.c_int),
         "golhip_comm_init": ([H, ctypes.c_char_p, i32, i32], ctypes.c_int),
         "golhip_comm_info": ([H, P(i32), P(i32), P(i32)], ctypes.c_int),
@@ -318,6 +319,11 @@ class Board:
 
     def set_option(self, key: str, value: int) -> None:
         _check(load().golhip_set_option(self._h, key.encode(), value))
+
+    def set_pad_step(self, mode: int) -> None:
+        """golhip_set_pad_step: widths that are no multiple of 32 on the fast
+        kernels as a padded torus: -1 the measured rule (default), 0 never, 1 always."""
+        _check(load().golhip_set_pad_step(self._h, mode))
 
     def set_stream(self, stream_ptr: int) -> None:
         _check(load().golhip_set_stream(self._h, ctypes.c_void_p(stream_ptr)))
@@ -652,6 +658,47 @@ def view_frame_np(words: np.ndarray, width: int, height: int, x0: int = 0, y0: i
     if fmt == VIEW_GRAY8:
         return g.astype(np.uint8)
     return (g * 0x01010101).astype(np.uint32)
+
+
+# --------------------------------------------------------------------------
+# the padded torus (golhip_set_pad_step; csrc/gol_pad_plan.h restated in numpy)
+# --------------------------------------------------------------------------
+def pad_plan_np(width: int) -> tuple[int, int, int]:
+    """(Wp, gR, gL) of a width-column board: Wp = roundup(width + 64, 64),
+    gR = ceil((Wp - width) / 2) ghost columns behind the last real column,
+    gL = Wp - width - gR in front of column 0 (the far end of the wide row)."""
+    wp = -(-(width + 64) // 64) * 64
+    pad = wp - width
+    return wp, (pad + 1) // 2, pad // 2
+
+
+def pad_src_cols_np(width: int) -> np.ndarray:
+    """The real column each of the Wp columns of the wide row holds."""
+    wp, gr, _ = pad_plan_np(width)
+    c = np.arange(wp, dtype=np.int64)
+    return np.where(c < width, c, np.where(c < width + gr, (c - width) % width, (c - wp) % width))
+
+
+def pad_run_np(board: np.ndarray, turns: int, depth: int, refresh_all: bool = True) -> np.ndarray:
+    """The padded torus' schedule on the host: the (H, W) 0/255 board widened
+    to Wp columns, then launches of at most `depth` turns of the plain torus
+    rule on the Wp x H torus with the ghost columns rewritten from the real
+    ones before each (refresh_all False: before the first alone, which goes
+    wrong once a stale ghost's error reaches a real column); the real columns
+    after `turns` turns."""
+    h, w = board.shape
+    src = pad_src_cols_np(w)
+    wide = (board == 255).astype(np.uint8)[:, src]
+    left = turns
+    while left > 0:
+        d = min(depth, left)
+        if refresh_all:
+            wide = wide[:, :w][:, src]
+        for _ in range(d):
+            n = sum(np.roll(np.roll(wide, dr, 0), dc, 1) for dr in (-1, 0, 1) for dc in (-1, 0, 1)) - wide
+            wide = ((n == 3) | ((wide == 1) & (n == 2))).astype(np.uint8)
+        left -= d
+    return (wide[:, :w] * 255).astype(np.uint8)
 
 
 # --------------------------------------------------------------------------

@@ -70,7 +70,8 @@ typedef struct golhip_perf {
     int32_t tb_depth;         /* most turns one step launch fuses (the setting,
                                  capped by the kernel's words per lane)       */
     int32_t rows_per_wave;    /* rows streamed per wavefront (full-depth launch)*/
-    int32_t kernel_variant;   /* 0 = generic (width % 32 != 0), 1 = bit-sliced*/
+    int32_t kernel_variant;   /* 0 = generic (width % 32 != 0), 1 = bit-sliced
+                                 (after a padded step: the wide board's)     */
     int32_t words_per_lane;   /* 1, 2 (interleaved pairs) or 4 (quads); 0 generic */
     int64_t persist_fallbacks; /* resident launches that timed out (not all workgroups
                                   co-resident) and were re-run on per-launch kernels */
@@ -82,7 +83,9 @@ typedef struct golhip_perf {
     int32_t persist_depth;    /* turns per super-step of the resident kernel (its
                                  depths stop at 16 for two words per lane)       */
     int32_t reserved0;
-    int64_t reserved1;        /* 0 (was split_launches: split tiling retired in round 5) */
+    int64_t pad_launches;     /* seam refreshes of the padded torus, one per launch of the
+                                 wide board (golhip_set_pad_step; the offset of the
+                                 retired split_launches / reserved1)             */
     int64_t skew_launches;    /* of step_launches, those that ran skewed band
                                  stacks (gol_skew_kernel, kernel_variant 3)     */
     int64_t halo_exchanges;   /* halo exchanges posted (RCCL ring)               */
@@ -202,6 +205,19 @@ int golhip_set_rows_per_wave(golhip_t h, int32_t rows);
  * Retired (refused as unknown keys): "split", "lds_split", "skew_nst",
  * "age_split", "overlap". */
 int golhip_set_option(golhip_t h, const char *key, int64_t value);
+/* The padded torus: a whole torus without a communicator whose width is no
+ * multiple of 32 may step on the fast per-launch kernels as a slightly wider
+ * torus (width rounded up to a multiple of 64 past width + 64) whose extra
+ * columns are ghost copies of real ones, refreshed before every launch; the
+ * board of this handle is whole again when golhip_step returns.  Results never
+ * depend on it.  mode -1 (the default): where it measured faster than the
+ * any-width kernel, by the board's cells and the turns of the call (DESIGN.md
+ * 5.17), falling back to that kernel if the wide board cannot be allocated;
+ * 0: never; 1: always (golhip_step then fails with GOLHIP_ENOMEM if the wide
+ * board cannot be allocated) -- GOLHIP_EINVAL on a strip, a ring or a handle
+ * whose width is a multiple of 32.  golhip_flip_stream / golhip_step_flips and
+ * strips keep the any-width kernel.  perf: pad_launches. */
+int golhip_set_pad_step(golhip_t h, int32_t mode);
 
 /* ---- multi-GPU -------------------------------------------------------- */
 /* RCCL ring of strips: rank r's neighbours are r-1 (rows above) and r+1

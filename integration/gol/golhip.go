@@ -80,6 +80,10 @@ package gol
 // static gh_status gh_checkpoint_load(golhip_t *hs, int32_t n, const char *path) {
 //     return gh_wrap(golhip_checkpoint_load(hs, n, path, NULL, NULL));
 // }
+// // The padded torus (int golhip_set_pad_step(golhip_t h, int32_t mode)): a width
+// // that is no multiple of 32 on the fast kernels; -1 the measured rule (the
+// // default, which the engine keeps), 0 never, 1 always.
+// static gh_status gh_set_pad_step(golhip_t h, int32_t mode) { return gh_wrap(golhip_set_pad_step(h, mode)); }
 import "C"
 
 import (
