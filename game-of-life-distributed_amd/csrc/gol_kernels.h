@@ -181,7 +181,9 @@ hipError_t launch_compact_scatter(const uint32_t *a, const uint32_t *b, int64_t 
                                   hipStream_t s, unsigned long long cap = ~0ull);
 
 // K5: one turn fused with its CellFlipped list (golhip_flip_stream): each
-// block steps 1024 consecutive words of the canonical board (W % 32 == 0),
+// block steps 1024 consecutive words of the canonical board (any W: where
+// W % 32 != 0 the row seam is closed in the row's first and last word,
+// gol_flip_seam.h, and the padding bits stay zero),
 // XORs old and new, finds its entries' offset with a single-pass decoupled
 // look-back over the blocks, and writes its entries row-major through LDS.
 // One launch per turn; the turn's lists append at run[0] and run[1] receives
@@ -256,7 +258,8 @@ struct FlipStreamArgs {
     long long timeout_ticks;        // one grid-wide wait (s_memrealtime, 100 MHz); past it: ctl[1]
 };
 hipError_t launch_flip_stream(const FlipStreamArgs &a, hipStream_t s);
-int flip_turn_blocks_per_cu(bool contig);
+// blocks of K5 a CU holds, for the instantiation a board launches (contig: Ww % 4 == 0; odd: W % 32 != 0)
+int flip_turn_blocks_per_cu(bool contig, bool odd);
 // golhip_group_flip_stream's gather: the batch's turns ran K5 on every strip
 // into the strip's own device list; this copies strip entries
 // [run[t], run[t + 1]) of every turn t < nturns to entry goff[t] of the

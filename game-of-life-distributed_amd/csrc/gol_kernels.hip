@@ -15,6 +15,7 @@
 #include "gol_kernels.h"
 #include "gol_bits.h"
 #include "gol_layout.h"
+#include "gol_flip_seam.h"
 
 #include <algorithm>
 #include <climits>
@@ -2491,7 +2492,10 @@ struct FtShared {
 // SC1 (K5r): every board and entry access is a write-through (sc1) buffer
 // access, the hand-off form that needs no fence (MI355X_MICROARCH.md, valid
 // forms); the block reports its turn done once its stores have drained.
-template <bool CONTIG, bool SC1>
+// ODD (W % 32 != 0): the row seam is closed in the row's first and last word
+// (gol_flip_seam.h): a ghost of column 0 in the last word, column W - 1 left
+// of the first, and the last word's padding bits cleared after the rule.
+template <bool CONTIG, bool SC1, bool ODD>
 __device__ __forceinline__ bool flip_turn_block(const FlipTurnArgs &a, const unsigned vid, FtShared &sh) {
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     // (unused, and dropped, without SC1)
@@ -2574,6 +2578,7 @@ __device__ __forceinline__ bool flip_turn_block(const FlipTurnArgs &a, const uns
     const unsigned Ww = (unsigned)a.Ww;
     const unsigned nwords = (unsigned)a.rows * Ww;  // host: < 2^32
     const unsigned base = vid * (unsigned)kFtWords;
+    const unsigned seam_r = (unsigned)a.W & 31u;  // (ODD only: 1..31)
 
     uint32_t flip[kFtK];
     unsigned long long packed = 0;  // CONTIG: the thread's count in field 0; else one 16-bit field per k
@@ -2605,7 +2610,11 @@ __device__ __forceinline__ bool flip_turn_block(const FlipTurnArgs &a, const uns
         uint32_t x[4][3], wv[4][3], ev[4][3];
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
-            const uint32_t v[4] = {q[j].x, q[j].y, q[j].z, q[j].w};
+            uint32_t v[4] = {q[j].x, q[j].y, q[j].z, q[j].w};
+            if constexpr (ODD) {
+                le[j] = c == 0 ? seam_left_word(le[j], seam_r) : le[j];
+                v[3] = c + 4 == Ww ? seam_last_word(v[3], re[j], seam_r) : v[3];
+            }
             uint32_t l = from_left_lane(v[3]), r = from_right_lane(v[0]);
             l = ledge ? le[j] : l;
             r = redge ? re[j] : r;
@@ -2620,6 +2629,12 @@ __device__ __forceinline__ bool flip_turn_block(const FlipTurnArgs &a, const uns
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             nx[k] = ft_rule(wv[k], x[k], ev[k]);
+            if constexpr (ODD) {
+                if (k == 3) {  // (the ghost bit of x[3][1] goes with the padding)
+                    nx[3] = c + 4 == Ww ? seam_clear_pad(nx[3], seam_r) : nx[3];
+                    x[3][1] = c + 4 == Ww ? seam_clear_pad(x[3][1], seam_r) : x[3][1];
+                }
+            }
             flip[k] = valid ? (nx[k] ^ x[k][1]) : 0u;
             cnt += (uint32_t)__builtin_popcount(flip[k]);
             alive_c += valid ? (uint32_t)__builtin_popcount(nx[k]) : 0u;
@@ -2653,13 +2668,21 @@ __device__ __forceinline__ bool flip_turn_block(const FlipTurnArgs &a, const uns
             }
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
+                if constexpr (ODD) {
+                    le[j] = c == 0 ? seam_left_word(le[j], seam_r) : le[j];
+                    x[j] = c == Ww - 1 ? seam_last_word(x[j], re[j], seam_r) : x[j];
+                }
                 uint32_t l = from_left_lane(x[j]), r = from_right_lane(x[j]);
                 l = ledge ? le[j] : l;
                 r = redge ? re[j] : r;
                 w[j] = __builtin_amdgcn_alignbit(x[j], l, 31);
                 e[j] = __builtin_amdgcn_alignbit(r, x[j], 1);
             }
-            const uint32_t nx = ft_rule(w, x, e);
+            uint32_t nx = ft_rule(w, x, e);
+            if constexpr (ODD) {  // (the ghost bit of x[1] goes with the padding)
+                nx = c == Ww - 1 ? seam_clear_pad(nx, seam_r) : nx;
+                x[1] = c == Ww - 1 ? seam_clear_pad(x[1], seam_r) : x[1];
+            }
             if constexpr (SC1) {
                 held[k] = nx;
                 held_at[k] = (size_t)(a.dst_base + (int)y) * Ww + c;
@@ -2899,7 +2922,7 @@ __device__ __forceinline__ bool flip_turn_block(const FlipTurnArgs &a, const uns
     return true;
 }
 
-template <bool CONTIG>
+template <bool CONTIG, bool ODD>
 __global__ __launch_bounds__(256) void gol_flip_turn_kernel(FlipTurnArgs a) {
     // copy blocks first in the grid: dispatched at once, their host stores
     // stream while the turn's blocks compute (behind them, they waited for
@@ -2921,7 +2944,7 @@ __global__ __launch_bounds__(256) void gol_flip_turn_kernel(FlipTurnArgs a) {
         __syncthreads();
         vid = s_vid;
     }
-    flip_turn_block<CONTIG, false>(a, vid, sh);
+    flip_turn_block<CONTIG, false, ODD>(a, vid, sh);
 }
 
 // K5r: the turns of a batch in one resident launch (flip_overlap 2; see
@@ -2939,7 +2962,7 @@ constexpr int kFtCopyBatch = 8;  // K5r copy blocks: 16-byte loads in flight a t
 #define GOL_K5R_NOCOPY 0  // diagnostic builds: K5r's copy blocks copy nothing (the turn loop's own time; WRONG host lists)
 #endif
 
-template <bool CONTIG>
+template <bool CONTIG, bool ODD>
 __global__ __launch_bounds__(256) void gol_flip_stream_kernel(FlipStreamArgs s) {
     __shared__ FtShared sh;
     __shared__ int s_go;
@@ -3105,7 +3128,7 @@ __global__ __launch_bounds__(256) void gol_flip_stream_kernel(FlipStreamArgs s) 
         a.turn = (unsigned)t;
         a.epoch = (s.epoch0 + (unsigned)t) & 0x3FFFFFu;
         a.alive = t == s.nturns - 1 ? s.alive : nullptr;
-        const bool more = flip_turn_block<CONTIG, true>(a, vid, sh);
+        const bool more = flip_turn_block<CONTIG, true, ODD>(a, vid, sh);
         __syncthreads();  // sh is reused by the next turn
         if (!more) return;  // (uniform: a turn not delivered ends the launch for this block)
     }
@@ -3113,30 +3136,46 @@ __global__ __launch_bounds__(256) void gol_flip_stream_kernel(FlipStreamArgs s) 
 
 int64_t flip_turn_blocks(int64_t nwords) { return (nwords + kFtWords - 1) / kFtWords; }
 
-int flip_turn_blocks_per_cu(bool contig) {
+// Calls f with the (CONTIG, ODD) pair of a board as compile-time constants.
+template <class F>
+static inline void ft_dispatch(bool contig, bool odd, F &&f) {
+    if (contig) {
+        if (odd) f(std::true_type{}, std::true_type{});
+        else f(std::true_type{}, std::false_type{});
+    } else {
+        if (odd) f(std::false_type{}, std::true_type{});
+        else f(std::false_type{}, std::false_type{});
+    }
+}
+
+int flip_turn_blocks_per_cu(bool contig, bool odd) {
     int b = 0;
-    const hipError_t e = contig ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, gol_flip_turn_kernel<true>, kFtThreads, 0)
-                                : hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, gol_flip_turn_kernel<false>, kFtThreads, 0);
+    hipError_t e = hipErrorUnknown;
+    ft_dispatch(contig, odd, [&](auto c, auto o) {
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, gol_flip_turn_kernel<decltype(c)::value, decltype(o)::value>,
+                                                         kFtThreads, 0);
+    });
     return e == hipSuccess ? b : 0;
 }
 
 hipError_t launch_flip_stream(const FlipStreamArgs &a, hipStream_t s) {
     const int64_t grid = (int64_t)a.turn.ncompute + a.ncopy;
     if (grid == 0 || a.nturns <= 0) return hipSuccess;
-    if (a.turn.Ww % 4 == 0)
-        hipLaunchKernelGGL(gol_flip_stream_kernel<true>, dim3((unsigned)grid), dim3(kFtThreads), 0, s, a);
-    else
-        hipLaunchKernelGGL(gol_flip_stream_kernel<false>, dim3((unsigned)grid), dim3(kFtThreads), 0, s, a);
+    ft_dispatch(a.turn.Ww % 4 == 0, a.turn.W % 32 != 0, [&](auto c, auto o) {
+        hipLaunchKernelGGL((gol_flip_stream_kernel<decltype(c)::value, decltype(o)::value>), dim3((unsigned)grid),
+                           dim3(kFtThreads), 0, s, a);
+    });
     return hipGetLastError();
 }
 
 hipError_t launch_flip_turn(const FlipTurnArgs &a, hipStream_t s) {
     const int64_t grid = (int64_t)a.ncompute + (a.cp_run ? a.cp_blocks : 0);
     if (grid == 0) return hipSuccess;
-    if (a.Ww % 4 == 0)
-        hipLaunchKernelGGL(gol_flip_turn_kernel<true>, dim3((unsigned)grid), dim3(kFtThreads), 0, s, a);
-    else
-        hipLaunchKernelGGL(gol_flip_turn_kernel<false>, dim3((unsigned)grid), dim3(kFtThreads), 0, s, a);
+    // (a copy-only launch carries no W: it runs no turn, any instantiation copies alike)
+    ft_dispatch(a.Ww % 4 == 0, a.W % 32 != 0, [&](auto c, auto o) {
+        hipLaunchKernelGGL((gol_flip_turn_kernel<decltype(c)::value, decltype(o)::value>), dim3((unsigned)grid),
+                           dim3(kFtThreads), 0, s, a);
+    });
     return hipGetLastError();
 }
 

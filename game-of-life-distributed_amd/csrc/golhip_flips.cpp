@@ -67,8 +67,9 @@ struct FlipBatch {
     golk::StepArgs sa;
 };
 
-// Generic widths (the 16 x 16 fixture) and giant strips: the three-pass
-// compaction one turn at a time, checked on the host after each turn.
+// Giant strips (2^32 - 4096 words or more, past K5's 32-bit word index): the
+// any-width kernel and the three-pass compaction one turn at a time, checked
+// on the host after each turn.
 static int flip_generic(golhip_t h, FlipBatch &b, int64_t *done_out, uint64_t *total_out) {
     const int64_t nw = b.nw, nturns = b.nturns;
     const uint64_t dcap = b.dcap;
@@ -269,9 +270,10 @@ static int flip_stream_locked(golhip_t h, int64_t nturns, int format, void *out,
     const int64_t t0 = h->turns;
     const int c0 = h->cur;
 
-    if (h->W % 32 != 0 || nw >= (1ll << 32) - 4096) return flip_generic(h, b, done_out, total_out);
+    if (nw >= (1ll << 32) - 4096) return flip_generic(h, b, done_out, total_out);
 
-    // fused turn + list (K5) on the canonical layout; into a golhip_host_alloc
+    // fused turn + list (K5) on the canonical layout, at any width (W % 32 != 0:
+    // the kernel closes the row seam itself, no padded torus); into a golhip_host_alloc
     // buffer the entries go without a host-side copy (option "flip_overlap"):
     //  2: K5r, the batch's turns in one resident launch whose copy blocks
     //     move each turn's list to the host while the next turns compute
@@ -282,7 +284,7 @@ static int flip_stream_locked(golhip_t h, int64_t nturns, int format, void *out,
     void *direct = b.direct = mapped_device_ptr(out, (size_t)dcap * esz);
     const int64_t nb = b.nb = golk::flip_turn_blocks(nw);
     const bool contig = h->Ww % 4 == 0;
-    const int bpc = std::min(golk::flip_turn_blocks_per_cu(contig), 4);
+    const int bpc = std::min(golk::flip_turn_blocks_per_cu(contig, h->W % 32 != 0), 4);
     // every block resident at once (with a 10 % margin): block order = blockIdx.
     // Not in a multi-rank ring: its fallback (restore, re-run in ticket order)
     // would redo the batch's exchanges on this rank alone and hang the ring.
@@ -409,8 +411,8 @@ static int group_sync(golhip_t *hs, int n) {
     return GOLHIP_OK;
 }
 
-// Generic widths and giant strips: one group turn at a time through the
-// three-pass compaction, the board's count checked on the host before the
+// Giant strips (2^32 - 4096 words or more): one group turn at a time through
+// the three-pass compaction, the board's count checked on the host before the
 // turn's entries are fetched (two synchronisations a turn); a turn that does
 // not fit is undone on every strip (its source board is still the other buffer).
 static int group_flip_generic(golhip_t *hs, int n, int64_t nturns, int format, void *out, uint64_t cap, uint64_t *counts,
@@ -462,7 +464,7 @@ static int group_flip_generic(golhip_t *hs, int n, int64_t nturns, int format, v
     return GOLHIP_OK;
 }
 
-// W % 32 == 0: per turn the group's 1-row halo exchange, then K5 on every
+// Every width: per turn the group's 1-row halo exchange, then K5 on every
 // strip's stream into the strip's own device list with its own running
 // offsets (no strip waits for another's); nothing is synchronised in the turn
 // loop.  Then the run arrays come back (first synchronisation), the merge
@@ -717,7 +719,7 @@ int golhip_group_flip_stream(golhip_t *hs, int32_t n, int64_t nturns, int32_t fo
         return fail(GOLHIP_EINVAL, "cell indices of a %dx%d board do not fit in 32 bits", hs[0]->W, hs[0]->H);
     std::vector<std::unique_lock<std::mutex>> locks;
     for (int i = 0; i < n; ++i) locks.emplace_back(hs[i]->mu);
-    bool fused = hs[0]->W % 32 == 0;
+    bool fused = true;  // (but for giant strips)
     for (int i = 0; i < n; ++i) {
         if (hs[i]->turns != hs[0]->turns)
             return fail(GOLHIP_EINVAL, "strip %d is at turn %lld, strip 0 at turn %lld", i, (long long)hs[i]->turns,

@@ -215,8 +215,11 @@ int golhip_set_option(golhip_t h, const char *key, int64_t value);
  * 5.17), falling back to that kernel if the wide board cannot be allocated;
  * 0: never; 1: always (golhip_step then fails with GOLHIP_ENOMEM if the wide
  * board cannot be allocated) -- GOLHIP_EINVAL on a strip, a ring or a handle
- * whose width is a multiple of 32.  golhip_flip_stream / golhip_step_flips and
- * strips keep the any-width kernel.  perf: pad_launches. */
+ * whose width is a multiple of 32.  It concerns golhip_step alone (and what
+ * steps through it): golhip_flip_stream, golhip_step_flips and
+ * golhip_group_flip_stream run every width on the fused turn + list kernel,
+ * which closes the row seam itself (no wide board, pad_launches stays 0); the
+ * steps of strips keep the any-width kernel.  perf: pad_launches. */
 int golhip_set_pad_step(golhip_t h, int32_t mode);
 
 /* ---- multi-GPU -------------------------------------------------------- */
@@ -346,11 +349,12 @@ int golhip_flip_stream(golhip_t h, int64_t nturns, int32_t format, void *out, ui
  * board-wide list would not fit in cap entries and leaves EVERY strip at that
  * turn (golhip_group_step / golhip_step* continue from there); if not even the
  * first turn fits: GOLHIP_ERANGE, nothing advanced, *n_entries = what it
- * needs.  widths that are a multiple of 32: K5 per strip and turn into device
+ * needs.  Every width: K5 per strip and turn into device
  * lists, no host synchronisation between turns, then one gather launch a
  * strip that writes `out` itself where it lies in golhip_host_alloc memory
- * mapped on the strip's device: two host round trips a call.  Other widths:
- * one group turn at a time (two round trips a turn).  With n == 1 and a
+ * mapped on the strip's device: two host round trips a call.  (Only strips of
+ * 2^32 - 4096 words or more go one group turn at a time through the any-width
+ * kernel, two round trips a turn.)  With n == 1 and a
  * whole-torus handle it is golhip_flip_stream.  In-process groups only (not
  * multi-rank rings). */
 int golhip_group_flip_stream(golhip_t *hs, int32_t n, int64_t nturns, int32_t format, void *out, uint64_t cap,
