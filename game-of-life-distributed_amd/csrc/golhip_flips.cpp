@@ -565,7 +565,7 @@ static int group_flip_fused(golhip_t *hs, int n, int64_t nturns, int format, voi
             h->alive_turn = -1;
         }
         if (done > 0)
-            if (int rc = group_step_locked(hs, n, done, 0, ready)) return rc;
+            if (int rc = group_step_locked(hs, n, done, 0, ready, false)) return rc;
     }
     // the gather: strip i's segments of the delivered turns to their places in
     // `out`, written by the strip's device where `out` is mapped on it, else

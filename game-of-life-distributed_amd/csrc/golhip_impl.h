@@ -20,7 +20,7 @@
 //   golhip_view.cpp     live view of one handle and of a group of strips (K7)
 //   golhip_options.cpp  the option table and its consent rules
 //   golhip_ckpt.cpp     checkpoints: shadow copy (K8), drain to a file, verified load
-//   golhip_pad.cpp      the padded torus: widths that are no multiple of 32 on the fast kernels
+//   golhip_pad.cpp      the padded torus and padded strips: widths that are no multiple of 32 on the fast kernels
 //
 // Everything here but `struct golhip` lives in namespace gh, whose symbols
 // are hidden: libgolhip.so exports the C-ABI of include/golhip.h alone.
@@ -267,6 +267,11 @@ struct golhip {
     golhip *wide = nullptr;
     int pad_mode = -1;        // golhip_set_pad_step: -1 the measured rule, 0 never, 1 always
     bool pad_nomem = false;   // the wide board could not be allocated: the rule stays on K1g
+    // padded strips (golhip_group_step[_ex]): every strip of a group whose
+    // width is no multiple of 32 owns the wide strip `wide` (Wp columns, this
+    // strip's row0 and rows, its own halo rows); the group decides from strip 0
+    int group_pad_mode = -1;        // golhip_group_set_pad_step: -1 the measured rule, 0 never, 1 always
+    bool group_pad_nomem = false;   // a wide strip of the group could not be allocated: the rule stays on K1g
 
     std::mutex mu;
 
@@ -347,7 +352,14 @@ int exchange_rccl(golhip_t h, int depth, hipStream_t st);
 int launch_depth(golhip_t h, int depth, bool count, bool halo);
 int step_checked_locked(golhip_t h, int64_t nturns, int32_t want_flips);
 int group_check(golhip_t *hs, int32_t n, bool need_board = true);  // need_board: every strip loaded
-int group_step_locked(golhip_t *hs, int32_t n, int64_t nturns, int32_t want_flips, hipEvent_t *keep = nullptr);
+// pad false: no padded strips (the flip stream's re-run of a stopped batch).
+int group_step_locked(golhip_t *hs, int32_t n, int64_t nturns, int32_t want_flips, hipEvent_t *keep = nullptr,
+                      bool pad = true);
+// The rounds of a group step: `turns` turns of the strips ss (a group's own
+// strips, or their wide strips with `owners` set: then a seam refresh of the
+// rows it reads goes before every launch, pad_seam), deep-halo exchanges
+// through `ready`.  count_last: the last launch leaves every strip's count.
+int group_rounds(golhip_t *ss, golhip_t *owners, int32_t n, int64_t turns, bool count_last, hipEvent_t *ready);
 // Halo rows of every strip from its ring neighbours' current boards, x rows
 // each way, by peer copies ordered through the n events `ready`.  relaunch:
 // several launches may follow before the next exchange, so every stream also
@@ -366,6 +378,15 @@ bool pad_wanted(golhip_t h, int64_t nturns);  // this step of nturns turns takes
 // board could not be had and the rule falls back to K1g.
 int pad_step(golhip_t h, int64_t nturns, bool *ran);
 int pad_destroy(golhip_t h);                 // the wide board, if any (golhip_destroy)
+// Padded strips: whether this group_step call of nturns turns pads (every strip or none) ...
+bool pad_group_wanted(golhip_t *hs, int32_t n, int64_t nturns);
+// ... and the call itself: pad, group_rounds over the wide strips, unpad with
+// every strip's own count.  *ran false (rc 0): a wide strip could not be had
+// and the rule falls back to K1g for the group's life.
+int pad_group_step(golhip_t *hs, int32_t n, int64_t nturns, hipEvent_t *ready, bool *ran);
+// The ghosts of the wide rows [lo, hi) of h's wide strip (relative to the
+// strip's first row; halo rows included), rewritten from their real columns.
+int pad_seam(golhip_t h, int lo, int hi);
 
 // ---- golhip_options.cpp -----------------------------------------------------
 bool tuning_env();      // GOLHIP_TUNING=1 (or GOLHIP_MEASUREMENT=1)

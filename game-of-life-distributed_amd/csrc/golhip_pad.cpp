@@ -3,6 +3,8 @@
 // Wp x H torus with ghost columns, refreshed between launches (gol_pad.hip),
 // instead of one turn a launch on K1g.  The wide board is an internal handle
 // of this one; the canonical board is whole again when a step returns.
+// The strips of a group (golhip_group_step) do the same with one wide strip
+// each, halo rows included: padded strips, the second half of this file.
 #include "golhip_impl.h"
 
 namespace gh GOLHIP_HIDDEN {
@@ -45,7 +47,8 @@ int pad_destroy(golhip_t h) {
     return golhip_destroy(w);
 }
 
-// The wide board: Wp x H on the owner's device and stream.
+// The wide board: Wp columns, the owner's rows of the torus (all of them, or
+// a strip's with its halo rows), on the owner's device and stream.
 static int ensure_wide(golhip_t h) {
     if (h->wide) return GOLHIP_OK;
     golk::PadPlan p;
@@ -54,7 +57,9 @@ static int ensure_wide(golhip_t h) {
     w->W = p.Wp;
     w->H = h->H;
     w->Ww = p.Wp / 32;
-    w->rows = h->H;
+    w->row0 = h->row0;
+    w->rows = h->rows;
+    w->strip = h->strip;
     w->device = h->device;
     w->flags = h->flags;
     w->stream = h->stream;
@@ -76,7 +81,7 @@ static int ensure_wide(golhip_t h) {
         (void)hipGetLastError();
         (void)golhip_destroy(w);
         const int code = e == hipErrorOutOfMemory ? GOLHIP_ENOMEM : GOLHIP_EHIP;
-        return fail(code, "padded torus %d x %d (%zu bytes x2): %s", p.Wp, h->H, bytes, hipGetErrorString(e));
+        return fail(code, "padded torus %d x %d (%zu bytes x2): %s", p.Wp, h->rows, bytes, hipGetErrorString(e));
     }
     h->wide = w;
     return GOLHIP_OK;
@@ -155,6 +160,134 @@ int pad_step(golhip_t h, int64_t nturns, bool *ran) {
     return GOLHIP_OK;
 }
 
+// ---- padded strips ------------------------------------------------------------
+// Every strip of a group owns a wide strip; a group_step call pads every
+// strip's own rows, runs the group's rounds over the wide strips (one deep-halo
+// exchange of k d wide rows, then k launches) and unpads.  The invariant:
+// every wide row a launch reads has had its ghosts rewritten from its own real
+// columns since it was last written, by a launch or by an exchange.  Exchanged
+// rows carry the neighbour's stale ghosts but exact real columns, so the seam
+// refresh before a launch covers the halo rows that launch reads too.
+
+// The measured rule of padded strips (profiles/strip_widths/bench_strip_widths.json,
+// DESIGN.md §5.17 "Padded strips"): per measured board, the fewest turns a call
+// from which mode 1 beat mode 0 in every repetition at 2, 4 and 8 strips alike
+// (and at every larger n measured).  A board takes the row of the largest
+// measured board that is no larger than it; boards below 100^2 take 100^2's.
+//   100^2    n = 1, 2 lost (0.82-0.96x, 0.88-1.08x), 4 won (1.06-1.33x)
+//   1000^2   n = 1, 2, 4 lost or tied at 4 or 8 strips (n = 4: 1.04-1.43x, not every repetition), 8 won (1.33-1.90x)
+//   5000^2   n = 1 tied at 4 and 8 strips (1.02-1.05x), 2 won (1.15-2.39x)
+//   10001^2  n = 1 won (1.76-3.80x); 16385^2 n = 1 won (2.77-6.95x)
+// The group pays a pad and an unpad launch a strip and a call beside K1g's one
+// launch a turn, so short calls of many small strips are launch-bound and lose.
+static constexpr PadRule kStripPadRule[] = {
+    {0, 4},
+    {1000ll * 1000, 8},
+    {5000ll * 5000, 2},
+    {10001ll * 10001, 1},
+};
+static bool strip_pad_auto(int64_t cells, int64_t nturns) {
+    int64_t min_turns = kStripPadRule[0].min_turns;
+    for (const PadRule &r : kStripPadRule)
+        if (cells >= r.min_cells) min_turns = r.min_turns;
+    return nturns >= min_turns;
+}
+
+static bool pad_group_applies(golhip_t *hs, int32_t n) {
+    golk::PadPlan p;
+    if (hs[0]->W % 32 == 0 || !golk::pad_plan(hs[0]->W, &p)) return false;
+    for (int i = 0; i < n; ++i)
+        if (hs[i]->ringed()) return false;
+    return true;
+}
+
+bool pad_group_wanted(golhip_t *hs, int32_t n, int64_t nturns) {
+    const int mode = hs[0]->group_pad_mode;
+    if (nturns < 1 || mode == 0 || !pad_group_applies(hs, n)) return false;
+    if (mode == 1) return true;
+    for (int i = 0; i < n; ++i)
+        if (hs[i]->group_pad_nomem) return false;
+    return strip_pad_auto((int64_t)hs[0]->W * hs[0]->H, nturns);
+}
+
+static golk::PadArgs pad_args(golhip_t h) {
+    golhip *w = h->wide;
+    golk::PadArgs a{};
+    golk::pad_plan(h->W, &a.plan);
+    a.canon = h->cur_rows();
+    a.wide = w->cur_rows();
+    a.rows = h->rows;
+    a.Ww = h->Ww;
+    a.Wwp = w->Ww;
+    return a;
+}
+
+int pad_seam(golhip_t h, int lo, int hi) {
+    golhip *w = h->wide;
+    // (the halo rows: kHalo above the strip's first row, kHalo below its last)
+    if (lo < -kHalo || hi > w->rows + kHalo || lo > hi) return fail(GOLHIP_EINVAL, "seam rows [%d, %d) of %d", lo, hi, w->rows);
+    golk::PadArgs a = pad_args(h);
+    a.canon = nullptr;
+    a.wide = w->buf[w->cur] + ((int64_t)kHalo + lo) * w->Ww;
+    a.rows = hi - lo;
+    HIP_OR_FAIL(golk::launch_seam(a, w->il, w->stream));
+    h->n.pad_launches++;
+    return GOLHIP_OK;
+}
+
+int pad_group_step(golhip_t *hs, int32_t n, int64_t nturns, hipEvent_t *ready, bool *ran) {
+    *ran = false;
+    for (int i = 0; i < n; ++i) {
+        HIP_OR_FAIL(hipSetDevice(hs[i]->device));
+        const int rc = ensure_wide(hs[i]);
+        if (!rc) continue;
+        if (hs[0]->group_pad_mode == 1 || rc != GOLHIP_ENOMEM) return rc;
+        // the rule: every strip or none, so the whole group stays on K1g from here on
+        for (int j = 0; j < n; ++j) {
+            hs[j]->group_pad_nomem = true;
+            HIP_OR_FAIL(hipSetDevice(hs[j]->device));
+            if (int prc = pad_destroy(hs[j])) return prc;
+        }
+        return GOLHIP_OK;
+    }
+    std::vector<golhip_t> ws((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        golhip *h = hs[i], *w = h->wide;
+        take_settings(h, w);
+        w->il = want_il(w);  // the pad kernel writes the layout the wide strips step in
+        w->loaded = true;
+        w->n = Counters{};
+        ws[i] = w;
+        if (w->il != hs[0]->wide->il) return fail(GOLHIP_EINVAL, "strip %d uses another word layout", i);
+    }
+    for (int i = 0; i < n; ++i) {
+        HIP_OR_FAIL(hipSetDevice(hs[i]->device));
+        HIP_OR_FAIL(golk::launch_pad(pad_args(hs[i]), ws[i]->il, hs[i]->stream));
+    }
+    if (int rc = group_rounds(ws.data(), hs, n, nturns, false, ready)) return rc;
+    for (int i = 0; i < n; ++i) {
+        golhip *h = hs[i], *w = ws[i];
+        HIP_OR_FAIL(hipSetDevice(h->device));
+        golk::PadArgs a = pad_args(h);
+        a.alive = h->d_scalars;  // the strip's own rows and real columns alone
+        HIP_OR_FAIL(hipMemsetAsync(h->d_scalars, 0, sizeof(unsigned long long), h->stream));
+        HIP_OR_FAIL(golk::launch_unpad(a, w->il, h->stream));
+        h->turns += nturns;
+        h->alive_turn = h->turns;
+        h->n.step_launches += w->n.step_launches;
+        h->n.step_turns += w->n.step_turns;
+        h->n.skew_launches += w->n.skew_launches;
+        h->n.skew_half_launches += w->n.skew_half_launches;
+        h->n.pair_launches += w->n.pair_launches;
+        h->n.pair_turns += w->n.pair_turns;
+        h->n.halo_bytes += w->n.halo_bytes;
+        h->n.halo_exchanges += w->n.halo_exchanges;
+        h->last_variant = w->last_variant;
+    }
+    *ran = true;
+    return GOLHIP_OK;
+}
+
 }  // namespace gh
 
 using namespace gh;
@@ -170,6 +303,21 @@ int golhip_set_pad_step(golhip_t h, int32_t mode) {
                                    "multiple of 32 (width %d, rows %d of %d)", h->W, h->rows, h->H);
     h->pad_mode = mode;
     h->pad_nomem = false;
+    return GOLHIP_OK;
+}
+
+int golhip_group_set_pad_step(golhip_t *hs, int32_t n, int32_t mode) {
+    if (int rc = group_check(hs, n, false)) return rc;
+    if (mode < -1 || mode > 1) return fail(GOLHIP_EINVAL, "pad step mode %d not in -1..1", mode);
+    std::vector<std::unique_lock<std::mutex>> locks;
+    for (int i = 0; i < n; ++i) locks.emplace_back(hs[i]->mu);
+    if (mode == 1 && !pad_group_applies(hs, n))
+        return fail(GOLHIP_EINVAL, "padded strips are for a group without a communicator whose width is no "
+                                   "multiple of 32 (width %d)", hs[0]->W);
+    for (int i = 0; i < n; ++i) {
+        hs[i]->group_pad_mode = mode;
+        hs[i]->group_pad_nomem = false;
+    }
     return GOLHIP_OK;
 }
 

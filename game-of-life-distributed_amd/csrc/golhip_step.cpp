@@ -560,11 +560,49 @@ int group_exchange(golhip_t *hs, int32_t n, int x, hipEvent_t *ready, bool relau
     return rc;
 }
 
+// The rounds of a group step over the strips ss: per round one deep-halo
+// exchange of k d rows and k launches of d turns, launch j over the rows
+// [-ext, rows + ext), ext = (k - 1 - j) d (a lone strip: torus launches, no
+// exchange).  owners: ss are the wide strips of these (padded strips,
+// golhip_pad.cpp), and every launch follows a seam refresh of the rows it reads.
+int group_rounds(golhip_t *ss, golhip_t *owners, int32_t n, int64_t turns, bool count_last, hipEvent_t *ready) {
+    int rc = GOLHIP_OK;
+    int64_t left = turns;
+    while (left > 0 && rc == GOLHIP_OK) {
+        int cap = GOLHIP_MAX_TB_DEPTH;
+        for (int i = 0; i < n; ++i) cap = std::min(cap, depth_cap(ss[i], n > 1));
+        const DepthRun run = depth_plan(cap, left);
+        const int d = run.d;
+        int k = 1;
+        if (n > 1) {
+            k = kHalo / d;
+            for (int i = 0; i < n; ++i) k = std::min(k, halo_launches(ss[i]->rows, d, run.n));
+            rc = group_exchange(ss, n, k * d, ready);
+        }
+        for (int j = 0; j < k && rc == GOLHIP_OK; ++j) {
+            const int ext = (k - 1 - j) * d;
+            const bool count = count_last && left - d == 0;
+            for (int i = 0; i < n && !rc; ++i) {
+                HIP_RC(hipSetDevice(ss[i]->device));
+                if (rc) break;
+                // a wide strip: the rows this launch reads (a lone strip is a torus: its own rows)
+                if (owners)
+                    rc = n > 1 ? pad_seam(owners[i], -(ext + d), ss[i]->rows + ext + d)
+                               : pad_seam(owners[i], 0, ss[i]->rows);
+                if (rc) break;
+                rc = n > 1 ? launch_ext(ss[i], d, count, ext) : launch_depth(ss[i], d, count, false);
+            }
+            left -= d;
+        }
+    }
+    return rc;
+}
+
 // The step of a checked group with every strip's mutex held.  `keep`
 // (golhip_group_view_stream): the caller's n events, left alive, and no
 // synchronisation at the end: the caller synchronises every stream and takes
 // the skew flags itself.
-int group_step_locked(golhip_t *hs, int32_t n, int64_t nturns, int32_t want_flips, hipEvent_t *keep) {
+int group_step_locked(golhip_t *hs, int32_t n, int64_t nturns, int32_t want_flips, hipEvent_t *keep, bool pad) {
     std::vector<hipEvent_t> ready(n, nullptr);
     int rc = GOLHIP_OK;
     for (int i = 0; i < n; ++i) {
@@ -582,27 +620,14 @@ int group_step_locked(golhip_t *hs, int32_t n, int64_t nturns, int32_t want_flip
     };
     const int64_t tail = (want_flips && nturns > 0) ? 1 : 0;
     int64_t left = nturns - tail;
-    while (left > 0 && rc == GOLHIP_OK) {
-        int cap = GOLHIP_MAX_TB_DEPTH;
-        for (int i = 0; i < n; ++i) cap = std::min(cap, depth_cap(hs[i], n > 1));
-        const DepthRun run = depth_plan(cap, left);
-        const int d = run.d;
-        int k = 1;
-        if (n > 1) {
-            k = kHalo / d;
-            for (int i = 0; i < n; ++i) k = std::min(k, halo_launches(hs[i]->rows, d, run.n));
-            exchange(k * d);
-        }
-        for (int j = 0; j < k && rc == GOLHIP_OK; ++j) {
-            for (int i = 0; i < n && !rc; ++i) {
-                HIP_RC(hipSetDevice(hs[i]->device));
-                if (rc) break;
-                rc = n > 1 ? launch_ext(hs[i], d, left - d == 0, (k - 1 - j) * d)
-                           : launch_depth(hs[i], d, left - d == 0, false);
-            }
-            left -= d;
-        }
+    if (!rc && pad && pad_group_wanted(hs, n, left)) {
+        // a width that is no multiple of 32 on the fast kernels, as padded strips
+        // (golhip_pad.cpp); the last turn of a want_flips step runs on K1g below
+        bool ran = false;
+        rc = pad_group_step(hs, n, left, ready.data(), &ran);
+        if (ran) left = 0;
     }
+    if (!rc && left > 0) rc = group_rounds(hs, nullptr, n, left, true, ready.data());
     if (tail && rc == GOLHIP_OK) {  // the last turn alone, then its flip list on every strip
         if (n > 1) exchange(1);
         for (int i = 0; i < n && !rc; ++i) {

@@ -153,6 +153,7 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "golhip_set_rows_per_wave": ([H, i32], ctypes.c_int),
         "golhip_set_option": ([H, ctypes.c_char_p, i64], ctypes.c_int),
         "golhip_set_pad_step": ([H, i32], ctypes.c_int),
+        "golhip_group_set_pad_step": ([P(H), i32, i32], ctypes.c_int),
         "golhip_comm_unique_id": ([ctypes.c_char_p], ctypes.c_int),
         "golhip_comm_init": ([H, ctypes.c_char_p, i32, i32], ctypes.c_int),
         "golhip_comm_info": ([H, P(i32), P(i32), P(i32)], ctypes.c_int),
@@ -547,6 +548,14 @@ def group_step(boards: list[Board], nturns: int, want_flips: bool = False) -> No
         _check(load().golhip_group_step(arr, len(boards), nturns))
 
 
+def group_set_pad_step(boards: list[Board], mode: int) -> None:
+    """golhip_group_set_pad_step: the strips of a group whose width is no
+    multiple of 32 on the fast kernels as padded strips: -1 the measured rule
+    (default), 0 never, 1 always."""
+    arr = (ctypes.c_void_p * len(boards))(*[b.handle for b in boards])
+    _check(load().golhip_group_set_pad_step(arr, len(boards), mode))
+
+
 def group_flip_stream(boards: list[Board], nturns: int, cap: int, fmt: int = FLIPS_XY, out: np.ndarray | None = None):
     """golhip_group_flip_stream: Board.flip_stream of the whole board that the
     strips `boards` (the group of group_step) hold: (entries, counts,
@@ -699,6 +708,86 @@ def pad_run_np(board: np.ndarray, turns: int, depth: int, refresh_all: bool = Tr
             wide = ((n == 3) | ((wide == 1) & (n == 2))).astype(np.uint8)
         left -= d
     return (wide[:, :w] * 255).astype(np.uint8)
+
+
+def group_halo_rounds(strip_rows, tb_depth: int, turns: int) -> list[tuple[int, int]]:
+    """The (depth, launches) rounds golhip_group_step runs `turns` turns of
+    two or more strips of `strip_rows` rows in, at one word per lane:
+    golhip_halo_schedule of the group's smallest strip.  (A lone strip is a
+    torus with no exchange: the same depths here, one launch a round.)"""
+    rounds, left = [], turns
+    while left > 0:
+        d, k = halo_schedule(min(strip_rows), tb_depth, left)
+        if len(strip_rows) == 1:
+            k = 1
+        rounds.append((d, k))
+        left -= d * k
+    return rounds
+
+
+def pad_group_run_np(board: np.ndarray, cuts, turns: int, rounds, seam: str = "window") -> np.ndarray:
+    """Padded strips (golhip_group_set_pad_step) on the host: the (H, W) 0/255
+    board on the row strips [cuts[i], cuts[i + 1]), each a wide strip of Wp
+    columns with HALO_ROWS halo rows above and below.  `rounds` is the (d, k)
+    schedule (sum of d k = turns): one exchange of k d wide rows each way, then
+    k launches of d turns, launch j over the rows [-e, rows + e) of the strip,
+    e = (k - 1 - j) d, from the rows [-(e + d), rows + e + d).  seam: which
+    ghosts are rewritten from their row's real columns before a launch --
+    "window": every row the launch reads (the scheme); "own": the strip's own
+    rows alone (the halo rows keep the neighbour's stale ghosts); "once": the
+    window, but before a round's first launch alone.  The real columns after
+    `turns` turns."""
+    if seam not in ("window", "own", "once"):
+        raise ValueError("seam must be window, own or once")
+    if sum(d * k for d, k in rounds) != turns:
+        raise ValueError("the rounds do not add up to turns")
+    h, w = board.shape
+    n, hr = len(cuts) - 1, HALO_ROWS
+    if n < 1 or cuts[0] != 0 or cuts[-1] != h or any(b <= a for a, b in zip(cuts[:-1], cuts[1:])):
+        raise ValueError("cuts must rise from 0 to the board's rows")
+    src = pad_src_cols_np(w)
+    rows = [b - a for a, b in zip(cuts[:-1], cuts[1:])]
+    strips = []
+    for a, b in zip(cuts[:-1], cuts[1:]):
+        s = np.zeros((b - a + 2 * hr, len(src)), dtype=np.uint8)
+        s[hr:hr + b - a] = (board[a:b] == 255).astype(np.uint8)[:, src]  # the pad pass
+        strips.append(s)
+
+    def life(x, wrap_rows):
+        p = x if wrap_rows else np.pad(x, ((1, 1), (0, 0)))
+        cnt = sum(np.roll(np.roll(p, dr, 0), dc, 1) for dr in (-1, 0, 1) for dc in (-1, 0, 1)) - p
+        out = ((cnt == 3) | ((p == 1) & (cnt == 2))).astype(np.uint8)
+        return out if wrap_rows else out[1:-1]
+
+    def refresh(s, lo, hi):  # rows [lo, hi) relative to the strip's first row
+        s[hr + lo:hr + hi] = s[hr + lo:hr + hi, :w][:, src]
+
+    for d, k in rounds:
+        x = k * d
+        if n > 1:
+            if x > hr or x > min(rows):
+                raise ValueError("a round exchanges more rows than a strip or its halo holds")
+            own = [s[hr:hr + r].copy() for s, r in zip(strips, rows)]
+            for i, s in enumerate(strips):
+                s[hr - x:hr] = own[(i - 1) % n][-x:]
+                s[hr + rows[i]:hr + rows[i] + x] = own[(i + 1) % n][:x]
+        for j in range(k):
+            e = (k - 1 - j) * d if n > 1 else 0
+            for i, s in enumerate(strips):
+                lo, hi = (-(e + d), rows[i] + e + d) if n > 1 else (0, rows[i])
+                if seam == "window" or (seam == "once" and j == 0):
+                    refresh(s, lo, hi)
+                elif seam == "own":
+                    refresh(s, 0, rows[i])
+                win = s[hr + lo:hr + hi].copy()
+                for _ in range(d):
+                    win = life(win, n == 1)
+                if n > 1:  # the rows d inside the window are exact: the launch's outputs
+                    s[hr - e:hr + rows[i] + e] = win[d:len(win) - d]
+                else:
+                    s[hr:hr + rows[i]] = win
+    out = np.concatenate([s[hr:hr + r, :w] for s, r in zip(strips, rows)])  # the unpad pass
+    return (out * 255).astype(np.uint8)
 
 
 # --------------------------------------------------------------------------

@@ -219,7 +219,8 @@ int golhip_set_option(golhip_t h, const char *key, int64_t value);
  * steps through it): golhip_flip_stream, golhip_step_flips and
  * golhip_group_flip_stream run every width on the fused turn + list kernel,
  * which closes the row seam itself (no wide board, pad_launches stays 0); the
- * steps of strips keep the any-width kernel.  perf: pad_launches. */
+ * strips of a group have golhip_group_set_pad_step, and a ring's steps keep
+ * the any-width kernel.  perf: pad_launches. */
 int golhip_set_pad_step(golhip_t h, int32_t mode);
 
 /* ---- multi-GPU -------------------------------------------------------- */
@@ -261,6 +262,21 @@ int golhip_group_step(golhip_t *hs, int32_t n, int64_t nturns);
  * strip order they are the board's row-major list).  Used by gol.Run with
  * GOL_NGPU / GOL_STRIPS (the row-strip decomposition behind the drop-in). */
 int golhip_group_step_ex(golhip_t *hs, int32_t n, int64_t nturns, int32_t want_flips);
+/* Padded strips: golhip_set_pad_step for the strips of a group.  Every strip
+ * of a group whose width is no multiple of 32 may step as a wide strip of the
+ * padded torus (its halo rows too: one deep-halo exchange of wide rows, then
+ * launches of up to 32 turns, the ghosts of the rows a launch reads refreshed
+ * before it); every strip's board is whole again when golhip_group_step[_ex]
+ * returns.  All strips pad or none does, decided once a call from the mode
+ * kept on strip 0: -1 (the default) where it measured faster than the
+ * any-width kernel, by the board's cells and the turns of the call (DESIGN.md
+ * 5.17), falling back to that kernel for the group's life if a wide strip
+ * cannot be allocated; 0: never; 1: always (the step then fails with
+ * GOLHIP_ENOMEM if a wide strip cannot be allocated) -- GOLHIP_EINVAL for a
+ * width that is a multiple of 32 or a strip with a communicator.  A
+ * want_flips step runs its last turn on the any-width kernel.  perf:
+ * pad_launches, one per launch of a wide strip. */
+int golhip_group_set_pad_step(golhip_t *hs, int32_t n, int32_t mode);
 
 /* Halo plan used by both transports (exposed for tests): rows this strip
  * sends up/down and receives for an exchange of `depth` rows

@@ -84,6 +84,11 @@ package gol
 // // that is no multiple of 32 on the fast kernels; -1 the measured rule (the
 // // default, which the engine keeps), 0 never, 1 always.
 // static gh_status gh_set_pad_step(golhip_t h, int32_t mode) { return gh_wrap(golhip_set_pad_step(h, mode)); }
+// // Padded strips (int golhip_group_set_pad_step(golhip_t *hs, int32_t n, int32_t mode)):
+// // the same for the strips of a group; the engine keeps the measured rule.
+// static gh_status gh_group_set_pad_step(golhip_t *hs, int32_t n, int32_t mode) {
+//     return gh_wrap(golhip_group_set_pad_step(hs, n, mode));
+// }
 import "C"
 
 import (
