@@ -40,6 +40,35 @@ std::string Event::String() const {
     }
 }
 
+RunOptions::Pattern ParsePattern(const std::string &spec) {
+    auto bad = [&](const char *what) {
+        return std::runtime_error("pattern \"" + spec + "\": " + what + " (expected path@x,y[,op], op one of copy|or|xor|clear)");
+    };
+    const size_t at = spec.rfind('@');
+    if (at == std::string::npos || at == 0) throw bad("no path@");
+    RunOptions::Pattern p;
+    p.path = spec.substr(0, at);
+    std::vector<std::string> f;
+    std::stringstream ss(spec.substr(at + 1));
+    for (std::string t; std::getline(ss, t, ',');) f.push_back(t);
+    if (f.size() < 2 || f.size() > 3) throw bad("bad position");
+    int64_t *out[2] = {&p.x, &p.y};
+    for (int i = 0; i < 2; ++i) {
+        char *end = nullptr;
+        const long long v = std::strtoll(f[i].c_str(), &end, 10);
+        if (f[i].empty() || *end) throw bad("bad position");
+        *out[i] = v;
+    }
+    if (f.size() == 3) {
+        static const char *const names[] = {"copy", "or", "xor", "clear"};
+        p.op = -1;
+        for (int i = 0; i < 4; ++i)
+            if (f[2] == names[i]) p.op = i;
+        if (p.op < 0) throw bad("unknown op");
+    }
+    return p;
+}
+
 // ---------------------------------------------------------------- PGM io
 // readPgmImage (io.go:90-126): whitespace-separated fields P5, W, H, 255;
 // the raster follows the single whitespace byte after maxval.
@@ -212,6 +241,15 @@ struct Engine {
     void load(const uint8_t *raster) {
         for (size_t i = 0; i < hs.size(); ++i) check(golhip_load_bytes(hs[i], raster + row0[i] * W));
     }
+    // patterns (RunOptions::blank, patterns): an empty board; a pattern file on the whole board
+    void clear() {
+        for (golhip_t h : hs) check(golhip_clear(h));
+    }
+    void stamp(const RunOptions::Pattern &p) {
+        if (golhip_stamp_file(hs.data(), (int32_t)hs.size(), p.path.c_str(), (int32_t)p.x, (int32_t)p.y, p.op, nullptr) !=
+            GOLHIP_OK)
+            throw std::runtime_error(golhip_last_error());
+    }
     void snapshot(uint8_t *out) {
         for (size_t i = 0; i < hs.size(); ++i) check(golhip_snapshot_bytes(hs[i], out + row0[i] * W));
     }
@@ -280,7 +318,23 @@ void Run(Params p, Chan<Event> *events, Chan<char32_t> *keyPresses, const RunOpt
     int64_t T0 = 0;
     std::vector<uint8_t> raster;
     const std::string image_path = opt.root + "/images/" + name + ".pgm";
-    if (opt.resume_path.empty() && stream) {
+    if (!opt.resume_path.empty() && (opt.blank || !opt.patterns.empty()))
+        throw std::runtime_error("resume: a run from a checkpoint takes neither blank nor patterns (a restarted job "
+                                 "must not stamp twice)");
+    // every pattern file's checks before a device is touched (golhip_pattern_info needs none)
+    for (const RunOptions::Pattern &ps : opt.patterns) {
+        golhip_pattern_info_t pi;
+        if (golhip_pattern_info(ps.path.c_str(), &pi) != GOLHIP_OK) throw std::runtime_error(golhip_last_error());
+        if (pi.width > W || pi.height > H)
+            throw std::runtime_error("pattern " + ps.path + " is " + std::to_string(pi.width) + " x " +
+                                     std::to_string(pi.height) + ": it does not fit the " + name + " board");
+        if (ps.x < 0 || ps.x >= W || ps.y < 0 || ps.y >= H)
+            throw std::runtime_error("pattern " + ps.path + ": corner (" + std::to_string(ps.x) + ", " +
+                                     std::to_string(ps.y) + ") is not on the " + name + " board");
+    }
+    if (opt.blank) {
+        // no image: the board starts empty (golhip_clear below)
+    } else if (opt.resume_path.empty() && stream) {
         // the header's checks before a device is touched, against this run's board so that they come in
         // ReadPgm's order (golhip_image_info has no board: its size checks would come too late); the
         // raster follows below, chunk by chunk, behind the same checks in golhip_image_load
@@ -303,7 +357,9 @@ void Run(Params p, Chan<Event> *events, Chan<char32_t> *keyPresses, const RunOpt
     }
 
     Engine board(W, H, opt);
-    if (opt.resume_path.empty() && stream) {
+    if (opt.blank) {
+        board.clear();
+    } else if (opt.resume_path.empty() && stream) {
         board.load_image(image_path);
         std::printf("File %s input done!\n", name.c_str());
         std::fflush(stdout);
@@ -315,6 +371,7 @@ void Run(Params p, Chan<Event> *events, Chan<char32_t> *keyPresses, const RunOpt
         std::fflush(stdout);
     }
     std::vector<uint8_t>().swap(raster);
+    for (const RunOptions::Pattern &ps : opt.patterns) board.stamp(ps);
 
     // Live view: frames land in the ring and are published by pointer.  With
     // cell events the turns keep the flip stream, in batches that end on the
@@ -835,6 +892,16 @@ int golrun_start_opts(int64_t turns, int64_t threads, int64_t width, int64_t hei
     if (opts->resume_path) o.resume_path = opts->resume_path;
     if (opts->reserved[1] != 0) o.stream_images = 1;
     o.image_every = opts->reserved[0];
+    o.blank = opts->reserved[3] != 0;
+    if (opts->reserved[2]) {  // one "path@x,y[,op]" a line
+        std::stringstream lines(reinterpret_cast<const char *>((uintptr_t)opts->reserved[2]));
+        try {
+            for (std::string line; std::getline(lines, line);)
+                if (!line.empty()) o.patterns.push_back(gol::ParsePattern(line));
+        } catch (const std::exception &e) {
+            return run_fail(e.what());
+        }
+    }
     golrun *r = new golrun((size_t)events_cap, (flags & GOLRUN_FLAG_KEYS) != 0);
     if (flags & GOLRUN_FLAG_VIEW_STRIPS) o.view_strips = 1;
     if (view) {

@@ -439,7 +439,28 @@ struct RunOptions {
     // before the final image is begun).  One image of the run is in flight at
     // a time, s / q images included: they queue, off the run's mutex.
     int64_t image_every = 0;
+    // Patterns (golhip_stamp_file): `blank` starts from an empty board
+    // (golhip_clear) instead of images/<W>x<H>.pgm; `patterns` are pattern
+    // files (RLE or PGM), stamped in order with their top-left corner at the
+    // torus cell (x, y), after the initial board is there and before anything
+    // is sent: the initial CellFlipped events are the alive cells of the board
+    // after the stamps.  A run on strips stamps through the group call.  An
+    // unreadable file, a pattern larger than the board or a corner off it ends
+    // the run with the parser's message where the image read fails, and so do
+    // patterns or `blank` beside resume_path: a restarted job must not stamp twice.
+    struct Pattern {
+        std::string path;
+        int64_t x = 0, y = 0;
+        int op = GOLHIP_STAMP_OR;
+    };
+    bool blank = false;
+    std::vector<Pattern> patterns;
 };
+
+// One "path@x,y[,op]" (op: copy | or | xor | clear, default or), as the
+// command line's -pattern and golrun_opts_t's spec give it.  Throws
+// std::runtime_error naming the spec.
+RunOptions::Pattern ParsePattern(const std::string &spec);
 
 // The PGM goroutine's file formats (io.go:42-126).
 std::vector<uint8_t> ReadPgm(const std::string &path, int64_t width, int64_t height);

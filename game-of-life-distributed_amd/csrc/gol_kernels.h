@@ -353,6 +353,22 @@ hipError_t launch_seam(const PadArgs &a, int il, hipStream_t s);
 // wide -> canon: the real columns, the last word's padding bits cleared.
 hipError_t launch_unpad(const PadArgs &a, int il, hipStream_t s);
 
+// gol_stamp.hip (K10): merges pattern columns [sx, sx + sw) of the nr pattern
+// rows `pat` (canonical words, pww a row; the bits of columns >= sx + sw are
+// not looked at) into columns [dx, dx + sw) of the local rows [row, row + nr)
+// of `rows` (layout il, Ww words a row; rows 8- / 16-byte aligned for il 2 /
+// 4).  op: GOLHIP_STAMP_*.  Nothing outside the rectangle is changed.  The
+// caller guarantees dx + sw <= W and sx + sw <= 32 pww; the grid is capped.
+struct StampArgs {
+    uint32_t *rows;
+    const uint32_t *pat;
+    int64_t row, nr;
+    int Ww, pww;
+    int dx, sx, sw;
+    int op;
+};
+hipError_t launch_stamp(const StampArgs &a, int il, hipStream_t s);
+
 // "NAME=value ..." of the build's tuning macros (golhip_build_info).
 const char *build_info();
 

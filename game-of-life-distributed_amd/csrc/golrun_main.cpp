@@ -4,7 +4,7 @@
 //   golrun [-t threads] [-w width] [-h height] [-turns n] [-noVis] [-root dir] [-device n]
 //          [-viewScale n] [-viewEvery n] [-viewDir dir] [-viewStrips]
 //          [-checkpoint path] [-checkpointEvery n] [-resume path]
-//          [-streamImages] [-imageEvery n]
+//          [-streamImages] [-imageEvery n] [-blank] [-pattern path@x,y[,op]]...
 //
 // Same flags, defaults and output as main.go: "Threads: / Width: / Height:"
 // lines, then gol.Run on images/<w>x<h>.pgm with an events channel of
@@ -29,6 +29,12 @@
 // a whole raster on the host; with it, -imageEvery <n> writes
 // out/<w>x<h>x<turn>.pgm at every turn that is a multiple of n
 // (gol_host.h RunOptions::stream_images, image_every).
+// -blank starts from an empty board instead of images/<w>x<h>.pgm; -pattern
+// path@x,y[,op] (repeatable; op one of copy|or|xor|clear, default or) stamps
+// a pattern file (RLE or PGM) with its top-left corner at the torus cell
+// (x, y), in the order given, before the first event (gol_host.h
+// RunOptions::blank, patterns).  A bad spec or an unreadable file ends the run
+// with the parser's message, before any event.
 // The headless drain loop ends at FinalTurnComplete (main.go:59-66) or when
 // the events channel closes.
 #include <sys/stat.h>
@@ -48,7 +54,8 @@ namespace {
 [[noreturn]] void usage(const char *msg) {
     std::fprintf(stderr, "golrun: %s\nusage: golrun [-t threads] [-w width] [-h height] [-turns n] [-noVis] "
                          "[-root dir] [-device n] [-viewScale n] [-viewEvery n] [-viewDir dir] [-viewStrips] "
-                         "[-checkpoint path] [-checkpointEvery n] [-resume path] [-streamImages] [-imageEvery n]\n", msg);
+                         "[-checkpoint path] [-checkpointEvery n] [-resume path] [-streamImages] [-imageEvery n] [-blank] "
+                         "[-pattern path@x,y[,op]]...\n", msg);
     std::exit(2);
 }
 
@@ -117,6 +124,15 @@ int main(int argc, char **argv) {
             opt.stream_images = (eq == std::string::npos || val == "true" || val == "1") ? 1 : 0;
         } else if (key == "-imageEvery") {
             opt.image_every = parse_int(value(), "imageEvery");
+        } else if (key == "-blank") {
+            opt.blank = eq == std::string::npos || val == "true" || val == "1";
+        } else if (key == "-pattern") {
+            try {
+                opt.patterns.push_back(gol::ParsePattern(value()));
+            } catch (const std::exception &e) {
+                std::fprintf(stderr, "golrun: %s\n", e.what());
+                return 1;
+            }
         } else {
             usage(("flag provided but not defined: " + key).c_str());
         }

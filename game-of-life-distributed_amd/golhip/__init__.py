@@ -27,6 +27,7 @@ MAX_TB_DEPTH = 32
 HALO_ROWS = 128  # GOLHIP_HALO_ROWS
 VIEW_ARGB, VIEW_GRAY8 = 0, 1  # GOLHIP_VIEW_ARGB8888, GOLHIP_VIEW_GRAY8
 VIEW_MAX_SCALE = 1024
+STAMP_COPY, STAMP_OR, STAMP_XOR, STAMP_CLEAR = 0, 1, 2, 3  # GOLHIP_STAMP_*
 
 
 class GolHipError(RuntimeError):
@@ -123,6 +124,16 @@ class ImageInfo(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+class PatternInfo(ctypes.Structure):
+    """golhip_pattern_info_t"""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("alive", ctypes.c_uint64),
+                ("format", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+    def as_dict(self) -> dict:
+        return {"width": self.width, "height": self.height, "alive": self.alive,
+                "format": "pgm" if self.format == 1 else "rle"}
+
+
 _lib = None
 
 # golhip_test_transport_fn (test hook): user, prev_rank, next_rank, send_up,
@@ -208,6 +219,12 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "golhip_image_load": ([P(H), i32, ctypes.c_char_p, P(CkptOpts), P(ImageInfo)], ctypes.c_int),
         "golhip_drain_wait": ([P(H), i32], ctypes.c_int),
         "golhip_test_image_expand": ([i32, ctypes.c_void_p, i32, i32, i32, i32, ctypes.c_void_p, u64], ctypes.c_int),
+        "golhip_clear": ([H], ctypes.c_int),
+        "golhip_stamp_bits": ([H, ctypes.c_void_p, i32, i32, i32, i32, i32], ctypes.c_int),
+        "golhip_group_stamp_bits": ([P(H), i32, ctypes.c_void_p, i32, i32, i32, i32, i32], ctypes.c_int),
+        "golhip_pattern_info": ([ctypes.c_char_p, P(PatternInfo)], ctypes.c_int),
+        "golhip_pattern_read": ([ctypes.c_char_p, ctypes.c_void_p, u64, P(PatternInfo)], ctypes.c_int),
+        "golhip_stamp_file": ([P(H), i32, ctypes.c_char_p, i32, i32, i32, P(PatternInfo)], ctypes.c_int),
         "golhip_perf": ([H, P(Perf)], ctypes.c_int),
         "golhip_perf_reset": ([H], ctypes.c_int),
         "golhip_persist_trace": ([H, P(u64)], ctypes.c_int),
@@ -398,6 +415,29 @@ class Board:
 
     def fill_random(self, seed: int) -> None:
         _check(load().golhip_fill_random(self._h, ctypes.c_uint64(seed)))
+
+    # patterns
+    def clear(self) -> None:
+        """golhip_clear: every cell dead, turn 0."""
+        _check(load().golhip_clear(self._h))
+
+    def stamp_bits(self, words, pw: int, ph: int, x0: int, y0: int, op: int = STAMP_COPY) -> None:
+        """golhip_stamp_bits: a pw x ph pattern of bit words ((ph, ceil(pw / 32))
+        uint32) with its top-left corner at the torus cell (x0, y0).  `words`
+        None passes a null pointer (the library refuses it)."""
+        if words is None:
+            _check(load().golhip_stamp_bits(self._h, None, pw, ph, x0, y0, op))
+            return
+        w = np.ascontiguousarray(words, dtype=np.uint32)
+        if w.size != max(ph, 0) * ((max(pw, 0) + 31) // 32):
+            raise ValueError(f"expected {ph} x {(pw + 31) // 32} words, got {w.shape}")
+        _check(load().golhip_stamp_bits(self._h, _ptr(w), pw, ph, x0, y0, op))
+
+    def stamp(self, cells, x0: int, y0: int, op: int = STAMP_COPY) -> None:
+        """Stamps a 2-D array of cells (alive where a bool is True or a uint8
+        is 255) with its top-left corner at the torus cell (x0, y0)."""
+        c = _alive_2d(cells)
+        self.stamp_bits(pattern_words_np(c), c.shape[1], c.shape[0], x0, y0, op)
 
     # turn loop
     def step(self, nturns: int, want_flips: bool = False) -> None:
@@ -1037,6 +1077,155 @@ def image_expand_hook(words: np.ndarray, width: int, row0: int, nrows: int, guar
     _check(load().golhip_test_image_expand(device, _ptr(w), width, w.shape[0], row0, nrows, _ptr(out), out.nbytes))
     return out[:nrows * width].tobytes(), out[nrows * width:].tobytes()
 
+# --------------------------------------------------------------------------
+# patterns
+# --------------------------------------------------------------------------
+def _alive_2d(cells) -> np.ndarray:
+    """A 2-D bool array: alive where a bool is True or a uint8 is 255."""
+    c = np.asarray(cells)
+    if c.ndim != 2:
+        raise ValueError(f"cells must be a 2-D array, got shape {c.shape}")
+    if c.dtype == np.bool_:
+        return c
+    if c.dtype == np.uint8:
+        return c == 255
+    raise ValueError(f"cells must be bool or uint8, got {c.dtype}")
+
+
+def pattern_words_np(cells) -> np.ndarray:
+    """The bit words golhip_stamp_bits takes: (ph, ceil(pw / 32)) uint32, cell
+    (r, c) = bit c % 32 of word c // 32 of row r, padding bits zero."""
+    c = _alive_2d(cells)
+    ph, pw = c.shape
+    ww = (pw + 31) // 32
+    bits = np.zeros((ph, ww * 32), dtype=np.uint8)
+    bits[:, :pw] = c
+    return np.packbits(bits, axis=1, bitorder="little").view("<u4").astype(np.uint32).reshape(ph, ww)
+
+
+def group_stamp(boards: list[Board], cells, x0: int, y0: int, op: int = STAMP_COPY) -> None:
+    """golhip_group_stamp_bits: Board.stamp on the board held by a group of strips."""
+    c = _alive_2d(cells)
+    w = pattern_words_np(c)
+    arr, n = _handles(boards)
+    _check(load().golhip_group_stamp_bits(arr, n, _ptr(w), c.shape[1], c.shape[0], x0, y0, op))
+
+
+def pattern_info(path: str) -> dict:
+    """golhip_pattern_info: width, height, alive and format ("rle" / "pgm") of a pattern file (no device)."""
+    info = PatternInfo()
+    _check(load().golhip_pattern_info(os.fsencode(path), ctypes.byref(info)))
+    return info.as_dict()
+
+
+def pattern_read(path: str) -> np.ndarray:
+    """golhip_pattern_read: the pattern file's cells as a (height, width) bool array (no device)."""
+    info = PatternInfo()
+    lib = load()
+    probe = np.zeros(1, dtype=np.uint32)
+    rc = lib.golhip_pattern_read(os.fsencode(path), _ptr(probe), 0, ctypes.byref(info))
+    if rc not in (GOLHIP_OK, GOLHIP_ERANGE):
+        _check(rc)
+    ww = (info.width + 31) // 32
+    words = np.zeros((info.height, ww), dtype=np.uint32)
+    _check(lib.golhip_pattern_read(os.fsencode(path), _ptr(words), words.size, ctypes.byref(info)))
+    bits = np.unpackbits(words.astype("<u4").view(np.uint8).reshape(info.height, ww * 4), axis=1, bitorder="little")
+    return bits[:, :info.width].astype(bool)
+
+
+def stamp_file(boards, path: str, x0: int, y0: int, op: int = STAMP_OR) -> dict:
+    """golhip_stamp_file: a pattern file onto one Board or a group of strips; returns pattern_info's dict."""
+    arr, n = _handles(boards)
+    info = PatternInfo()
+    _check(load().golhip_stamp_file(arr, n, os.fsencode(path), x0, y0, op, ctypes.byref(info)))
+    return info.as_dict()
+
+
+# Numpy restatements for the tests; they share no code with the C++.
+def rle_parse_np(text: str) -> np.ndarray:
+    """The cells of RLE text as a (y, x) bool array.  Raises ValueError where
+    the library refuses the file."""
+    lines = text.split("\n")
+    k = 0
+    while k < len(lines) and (lines[k].strip() == "" or lines[k].lstrip().startswith("#")):
+        k += 1
+    head = re.fullmatch(r"x=(-?\d+),y=(-?\d+)(?:,rule=(\S+))?", "".join(lines[k].split()) if k < len(lines) else "")
+    if not head:
+        raise ValueError("no header")
+    w, h, rule = int(head.group(1)), int(head.group(2)), head.group(3)
+    if rule is not None and rule.upper() not in ("B3/S23", "23/3"):
+        raise ValueError("rule")
+    if not (1 <= w < 2 ** 31 and 1 <= h < 2 ** 31):
+        raise ValueError("size")
+    body = "".join("".join(lines[k + 1:]).split())
+    if "!" not in body:
+        raise ValueError("no !")
+    body = body[:body.index("!")]
+    cells = np.zeros((h, w), dtype=bool)
+    x = y = 0
+    for cnt, tag in re.findall(r"(\d*)(\D)", body):
+        n = int(cnt) if cnt else 1
+        if tag == "$":
+            y, x = y + n, 0
+        elif tag in "bo":
+            if y >= h or x + n > w:
+                raise ValueError("run leaves the box")
+            if tag == "o":
+                cells[y, x:x + n] = True
+            x += n
+        else:
+            raise ValueError("unknown character")
+    return cells
+
+
+def rle_format_np(cells) -> str:
+    """RLE text of a 2-D array of cells: header, runs with trailing dead cells
+    and rows left out, lines of at most 70 characters."""
+    c = _alive_2d(cells)
+    h, w = c.shape
+    toks, pending = [], 0  # pending: row ends not yet written
+    for y in range(h):
+        row = c[y]
+        if row.any():
+            if pending:
+                toks.append(("$", pending))
+                pending = 0
+            last = int(np.flatnonzero(row)[-1])
+            x = 0
+            while x <= last:
+                e = x
+                while e <= last and row[e] == row[x]:
+                    e += 1
+                toks.append(("o" if row[x] else "b", e - x))
+                x = e
+        pending += 1
+    out, line = [f"x = {w}, y = {h}, rule = B3/S23"], ""
+    for tag, n in toks + [("!", 1)]:
+        t = (str(n) if n > 1 else "") + tag
+        if len(line) + len(t) > 70:
+            out.append(line)
+            line = ""
+        line += t
+    out.append(line)
+    return "\n".join(out) + "\n"
+
+
+def stamp_np(board_cells, cells, x0: int, y0: int, op: int = STAMP_COPY) -> np.ndarray:
+    """What a stamp leaves: a copy of the (H, W) board (bool, or uint8 with 255
+    alive; the result has the same dtype) with the pattern merged at the
+    torus cell (x0, y0), wrapping in x and y."""
+    b = np.array(board_cells, copy=True)
+    alive = _alive_2d(b).copy()
+    p = _alive_2d(cells)
+    H, W = alive.shape
+    ys = (y0 + np.arange(p.shape[0])) % H
+    xs = (x0 + np.arange(p.shape[1])) % W
+    cur = alive[np.ix_(ys, xs)]
+    new = {STAMP_COPY: p, STAMP_OR: cur | p, STAMP_XOR: cur ^ p, STAMP_CLEAR: cur & ~p}[op]
+    alive[np.ix_(ys, xs)] = new
+    if b.dtype == np.bool_:
+        return alive
+    return np.where(alive, 255, 0).astype(np.uint8)
 
 
 # --------------------------------------------------------------------------
@@ -1114,7 +1303,8 @@ class Run:
     def __init__(self, turns: int, threads: int, width: int, height: int, root: str, *, device: int = 0,
                  keys: bool = False, quirks: bool = False, cell_events: bool = True, turn_events: bool = True,
                  events_cap: int = 0, ticker_ms: int = 0, view: dict | None = None, checkpoint: dict | None = None,
-                 resume: str | None = None, stream_images: bool = False, image_every: int = 0):
+                 resume: str | None = None, stream_images: bool = False, image_every: int = 0, blank: bool = False,
+                 patterns=None):
         """view: the live view (golrun_start_view), dict(scale=..., every=1,
         x0=0, y0=0, out_w=None, out_h=None, fmt=VIEW_ARGB, strips=False);
         missing out_w / out_h are the largest that fit.  Run.view_frame()
@@ -1126,11 +1316,26 @@ class Run:
         (golrun_start_opts).  stream_images: images/ and out/ files through
         golhip_image_* (the load in chunks, every image written behind the
         turns); image_every: with it, out/<W>x<H>x<turn>.pgm at every turn that
-        is a multiple of it."""
+        is a multiple of it.  blank: start from an empty board instead of
+        images/<W>x<H>.pgm.  patterns: [(path, x, y[, op]), ...], pattern
+        files (RLE or PGM) stamped in order, top-left corner at the torus cell
+        (x, y), after the initial board is there and before any event; op is
+        "copy", "or" (the default), "xor" or "clear" (or a STAMP_* number)."""
         lib = load_host()
         flags = (FLAG_KEYS if keys else 0) | (FLAG_REF_QUIRKS if quirks else 0) | \
             (0 if cell_events else FLAG_NO_CELL_EVENTS) | (0 if turn_events else FLAG_NO_TURN_EVENTS)
-        more = checkpoint is not None or resume is not None or stream_images or image_every != 0  # golrun_start_opts
+        more = checkpoint is not None or resume is not None or stream_images or image_every != 0 or blank or \
+            bool(patterns)  # golrun_start_opts
+        spec = None
+        if patterns:
+            ops = {STAMP_COPY: "copy", STAMP_OR: "or", STAMP_XOR: "xor", STAMP_CLEAR: "clear"}
+            rows = []
+            for pat in patterns:
+                if len(pat) not in (3, 4) or "\n" in os.fspath(pat[0]):
+                    raise ValueError("a pattern is (path, x, y[, op])")
+                op = pat[3] if len(pat) == 4 else "or"
+                rows.append(f"{os.fspath(pat[0])}@{int(pat[1])},{int(pat[2])},{ops.get(op, op)}")
+            spec = ctypes.create_string_buffer("\n".join(rows).encode())
         h = ctypes.c_void_p()
         self._view = None
         if checkpoint is not None and (set(checkpoint) - {"path", "every"} or "path" not in checkpoint):
@@ -1148,6 +1353,8 @@ class Run:
                 ro.resume_path = os.fsencode(resume)
             ro.reserved[0] = int(image_every)
             ro.reserved[1] = 1 if stream_images else 0
+            ro.reserved[2] = ctypes.addressof(spec) if spec is not None else 0  # (copied before the call returns)
+            ro.reserved[3] = 1 if blank else 0
         if view is not None:
             unknown = set(view) - {"scale", "every", "x0", "y0", "out_w", "out_h", "fmt", "strips"}
             if unknown or "scale" not in view:

@@ -583,6 +583,79 @@ int golhip_drain_wait(golhip_t *hs, int32_t n);
 int golhip_test_image_expand(int32_t device, const uint32_t *words, int32_t width, int32_t nrows, int32_t row0,
                              int32_t nr, uint8_t *out, uint64_t out_bytes);
 
+/* ---- patterns ----------------------------------------------------------- */
+/* An empty board, and a rectangle of cells stamped anywhere on the torus: the
+ * way to put a prepared pattern (a glider gun, a fleet, an experiment) on a
+ * board too large to load as an image.  The stamp runs on the device, in the
+ * layout the board is stepped in, at turn 0 or mid-run; results never depend
+ * on the words per lane, the padded torus, the strip count or the launch plan.
+ *
+ * golhip_clear: every cell of this handle's rows dead; it ends as
+ * golhip_load_bits ends: turn 0, count and flip list dropped.
+ *
+ * golhip_stamp_bits: `words` is a pattern of pw x ph cells as bit words, ph
+ * rows of ceil(pw / 32) uint32 (cell (r, c) = bit c % 32 of word c / 32 of row
+ * r; the bits of columns >= pw in a row's last word are ignored).  Its
+ * top-left corner goes to the torus cell (x0, y0): pattern cell (r, c) meets
+ * board cell ((y0 + r) mod height, (x0 + c) mod width).  Inside that rectangle
+ *   GOLHIP_STAMP_COPY   the board becomes the pattern, dead cells included;
+ *   GOLHIP_STAMP_OR     cells alive in the pattern come alive;
+ *   GOLHIP_STAMP_XOR    cells alive in the pattern flip;
+ *   GOLHIP_STAMP_CLEAR  cells alive in the pattern die;
+ * cells outside it are never written.  Required: 0 <= x0 < width, 0 <= y0 <
+ * height, 1 <= pw <= width, 1 <= ph <= height (at most one lap, which may
+ * cross both seams); anything else is GOLHIP_EINVAL, and so are an unknown op,
+ * a null pointer and a board never loaded: the board is then unchanged.
+ * The turn does not change: a stamp edits the board at the turn it is at.  The
+ * alive count and the flip list the handle keeps are dropped as a load drops
+ * them (the next golhip_alive_count recounts).  The call stages the words in
+ * device scratch (the buffer is not retained), runs behind whatever is
+ * enqueued on the handle's stream (a checkpoint or image begun earlier shows
+ * the board as it was before the stamp) and synchronises the stream before it
+ * returns.  On a strip handle y counts torus rows, and pattern rows that fall
+ * on rows the strip does not own are skipped (halo rows are not written: every
+ * step exchanges them before its first launch; a rank of a ring is a strip
+ * like any other).  golhip_group_stamp_bits stamps the board held by the group
+ * of row strips golhip_group_step takes: every strip takes its rows. */
+#define GOLHIP_STAMP_COPY 0
+#define GOLHIP_STAMP_OR 1
+#define GOLHIP_STAMP_XOR 2
+#define GOLHIP_STAMP_CLEAR 3
+int golhip_clear(golhip_t h);
+int golhip_stamp_bits(golhip_t h, const uint32_t *words, int32_t pw, int32_t ph, int32_t x0, int32_t y0, int32_t op);
+int golhip_group_stamp_bits(golhip_t *hs, int32_t n, const uint32_t *words, int32_t pw, int32_t ph,
+                            int32_t x0, int32_t y0, int32_t op);
+/* Pattern files, told apart by their first bytes, not their names: a PGM
+ * image ("P5", alive <=> byte 255, the checks and messages of
+ * golhip_image_info) or else RLE, the run-length format Life programs
+ * exchange: '#' lines, the header "x = m, y = n[, rule = r]", then runs
+ * <count><b|o|$> ended by '!', white space anywhere between the body's
+ * characters, trailing dead cells and rows optional.  Only Conway's rule is
+ * read: B3/S23 (either case), 23/3, or none.  GOLHIP_EINVAL with a message
+ * naming the check: no header, another rule, a size outside 1 .. 2^31 - 1, a
+ * run that leaves the x by y box, an unknown character, no '!' before the end
+ * of the file (and a file that cannot be opened). */
+typedef struct golhip_pattern_info {
+    int32_t width, height;
+    uint64_t alive;
+    int32_t format;        /* 0 RLE, 1 PGM */
+    int32_t reserved;
+} golhip_pattern_info_t;
+/* Size, alive cells and format of a pattern file: the whole body is parsed in
+ * one pass and nothing of the size of width * height is allocated.  Needs no
+ * device. */
+int golhip_pattern_info(const char *path, golhip_pattern_info_t *info);
+/* The pattern as golhip_stamp_bits takes it: height * ceil(width / 32) words
+ * (padding bits zero).  GOLHIP_ERANGE when cap_words is smaller, with
+ * info->width and height set (alive 0): the size is checked before anything is
+ * written.  Needs no device. */
+int golhip_pattern_read(const char *path, uint32_t *words, uint64_t cap_words, golhip_pattern_info_t *info);
+/* golhip_pattern_read and golhip_group_stamp_bits in one call (hs, n: one
+ * whole-torus handle or a group of strips).  A pattern larger than the board
+ * is refused before its cells are read.  info nullable. */
+int golhip_stamp_file(golhip_t *hs, int32_t n, const char *path, int32_t x0, int32_t y0, int32_t op,
+                      golhip_pattern_info_t *info);
+
 /* ---- measurement ------------------------------------------------------ */
 int golhip_perf(golhip_t h, golhip_perf_t *out);
 /* Diagnostics of the persistent step kernels since the last call (option

@@ -94,7 +94,20 @@ int golrun_start_view(int64_t turns, int64_t threads, int64_t width, int64_t hei
  * reserved[0]: image_every (gol_host.h RunOptions::image_every; 0: none): with
  * streamed images, out/<W>x<H>x<turn>.pgm at every turn that is a multiple of
  * it, behind the following turns, each with its ImageOutputComplete once the
- * file is complete.  Without streamed images the run fails with a message. */
+ * file is complete.  Without streamed images the run fails with a message.
+ * reserved[2]: patterns (gol_host.h RunOptions::patterns; 0: none): a pointer
+ * (cast to int64_t) to a NUL-terminated string with one "path@x,y[,op]" a
+ * line, op one of copy|or|xor|clear (default or): pattern files (RLE or PGM,
+ * golhip_stamp_file) stamped in that order, top-left corner at the torus cell
+ * (x, y), after the initial board is there and before any event; the initial
+ * CellFlipped events are the alive cells of the board after the stamps.  The
+ * string is copied before golrun_start_opts returns; a spec that does not
+ * parse fails the call itself (golrun_last_error), an unreadable file or a
+ * pattern that does not fit fails the run where the image read fails.
+ * reserved[3]: blank (RunOptions::blank): 1 starts from an empty board
+ * (golhip_clear) instead of images/<W>x<H>.pgm.
+ * With resume_path, patterns and blank are refused where the image read
+ * fails: a restarted job must not stamp twice. */
 typedef struct golrun_opts {
     const golhip_view_t *view;
     int32_t view_every;
@@ -102,7 +115,7 @@ typedef struct golrun_opts {
     const char *checkpoint_path;
     int64_t checkpoint_every;
     const char *resume_path;
-    int64_t reserved[4];    /* [0]: image_every; [1]: stream_images; the rest zero */
+    int64_t reserved[4];    /* [0]: image_every; [1]: stream_images; [2]: patterns; [3]: blank */
 } golrun_opts_t;
 int golrun_start_opts(int64_t turns, int64_t threads, int64_t width, int64_t height, const char *root,
                       int32_t device, uint32_t flags, int32_t events_cap, int32_t ticker_ms,

@@ -93,6 +93,18 @@ package gol
 // static gh_status gh_image_load(golhip_t *hs, int32_t n, const char *path) {
 //     return gh_wrap(golhip_image_load(hs, n, path, NULL, NULL));
 // }
+// // Patterns (golhip_clear, golhip_stamp_bits, golhip_stamp_file): an empty
+// // board, and a rectangle of cells stamped anywhere on the torus at the turn the
+// // board is at; the group calls take one whole-torus handle as well.
+// static gh_status gh_clear(golhip_t h) { return gh_wrap(golhip_clear(h)); }
+// static gh_status gh_group_stamp_bits(golhip_t *hs, int32_t n, const uint32_t *words, int32_t pw, int32_t ph,
+//                                      int32_t x0, int32_t y0, int32_t op) {
+//     return gh_wrap(golhip_group_stamp_bits(hs, n, words, pw, ph, x0, y0, op));
+// }
+// static gh_status gh_stamp_file(golhip_t *hs, int32_t n, const char *path, int32_t x0, int32_t y0, int32_t op,
+//                                golhip_pattern_info_t *info) {
+//     return gh_wrap(golhip_stamp_file(hs, n, path, x0, y0, op, info));
+// }
 // // The padded torus (int golhip_set_pad_step(golhip_t h, int32_t mode)): a width
 // // that is no multiple of 32 on the fast kernels; -1 the measured rule (the
 // // default, which the engine keeps), 0 never, 1 always.
@@ -202,6 +214,46 @@ func loadImageEngine(p Params, path string) *engine {
 		panic(C.GoString(&s.msg[0]))
 	}
 	return e
+}
+
+// Stamp ops (GOLHIP_STAMP_*): what a pattern does to the cells of its rectangle.
+const (
+	StampCopy  = 0 // the rectangle becomes the pattern, dead cells included
+	StampOr    = 1 // cells alive in the pattern come alive
+	StampXor   = 2 // cells alive in the pattern flip
+	StampClear = 3 // cells alive in the pattern die
+)
+
+// Clear leaves every cell of the board dead at turn 0 (golhip_clear on every strip).
+func (e *engine) Clear() {
+	for _, h := range e.hs {
+		check(C.gh_clear(h))
+	}
+}
+
+// StampBits merges a pw x ph pattern of bit words (ph rows of ceil(pw/32)
+// words, cell (r, c) = bit c%32 of word c/32 of row r) into the board with its
+// top-left corner at the torus cell (x0, y0); the turn does not change
+// (golhip_group_stamp_bits).  words is only read during the call.
+func (e *engine) StampBits(words []uint32, pw, ph, x0, y0, op int) {
+	if len(words) < ph*((pw+31)/32) || len(words) == 0 {
+		panic("StampBits: words shorter than the pattern")
+	}
+	check(C.gh_group_stamp_bits((*C.golhip_t)(unsafe.Pointer(&e.hs[0])), C.int32_t(len(e.hs)),
+		(*C.uint32_t)(unsafe.Pointer(&words[0])), C.int32_t(pw), C.int32_t(ph), C.int32_t(x0), C.int32_t(y0), C.int32_t(op)))
+}
+
+// StampFile stamps a pattern file (RLE, or a PGM with alive = 255; told apart
+// by the first bytes) and returns its width, height and alive cells
+// (golhip_stamp_file).  A file that does not parse or fit panics with the
+// parser's message.
+func (e *engine) StampFile(path string, x0, y0, op int) (width, height int, alive uint64) {
+	cpath := C.CString(path)
+	defer C.free(unsafe.Pointer(cpath))
+	var info C.golhip_pattern_info_t
+	check(C.gh_stamp_file((*C.golhip_t)(unsafe.Pointer(&e.hs[0])), C.int32_t(len(e.hs)), cpath, C.int32_t(x0), C.int32_t(y0),
+		C.int32_t(op), &info))
+	return int(info.width), int(info.height), uint64(info.alive)
 }
 
 // imageBegin starts the image of the board at its current turn
