@@ -461,6 +461,8 @@ int golhip_checkpoint_load(golhip_t *hs, int32_t n, const char *path, const golh
         h->turns = fi.turn;
         h->alive_turn = -1;
         h->flips_valid = false;
+        h->ft_est = 0;  // a new board (as loaded_canonical)
+        h->group_ft_est = 0;
         alive += h->h_scalars[2];
         hash += h->h_scalars[3];
     }

@@ -12,13 +12,21 @@ namespace gh GOLHIP_HIDDEN {
 static constexpr int kFlipStreamCopyBlocks = 128;
 static constexpr int64_t kFlipStreamMinBlocks = 64;  // (64 K words, e.g. 1448^2)
 
-int start_flips(golhip_t h) {
+// Count and scan of the flip list (current against previous board) into d_blk
+// and d_scalars[1]: what finish_compact scatters from.
+static int count_flips(golhip_t h) {
     const int64_t nw = h->local_words();
     const int64_t nb = golk::compact_blocks(nw);
     int rc = h->d_blk.ensure(h, nb);
     if (rc) return rc;
     HIP_OR_FAIL(golk::launch_compact_count(h->cur_rows(), h->prev_rows(), nw, h->d_blk.p, h->stream));
     HIP_OR_FAIL(golk::launch_compact_scan(h->d_blk.p, nb, h->d_scalars + 1, h->stream));
+    h->flips_counted = true;
+    return GOLHIP_OK;
+}
+
+int start_flips(golhip_t h) {
+    if (int rc = count_flips(h)) return rc;
     h->flips_valid = true;
     h->flips_turn = h->turns;
     return GOLHIP_OK;
@@ -645,6 +653,10 @@ int golhip_flips(golhip_t h, int32_t *xy, uint64_t cap, uint64_t *n) {
         if (n) *n = 0;
         return fail(GOLHIP_EINVAL, "no flip list: step with want_flips first");
     }
+    // golhip_alive_cells took d_blk and the total for its own list: both boards
+    // of the difference are intact, so count and scan again
+    if (!h->flips_counted)
+        if (int rc = count_flips(h)) return rc;
     return finish_compact(h, h->cur_rows(), h->prev_rows(), xy, cap, n);
 }
 
@@ -763,7 +775,7 @@ int golhip_alive_cells(golhip_t h, int32_t *xy, uint64_t cap, uint64_t *n) {
     if (int rc = h->d_blk.ensure(h, nb)) return rc;
     HIP_OR_FAIL(golk::launch_compact_count(h->cur_rows(), nullptr, nw, h->d_blk.p, h->stream));
     HIP_OR_FAIL(golk::launch_compact_scan(h->d_blk.p, nb, h->d_scalars + 1, h->stream));
-    h->flips_valid = false;  // d_blk reused
+    h->flips_counted = false;  // d_blk and the total reused: golhip_flips counts again
     return finish_compact(h, h->cur_rows(), nullptr, xy, cap, n);
 }
 

@@ -75,6 +75,9 @@ int set_layout(golhip_t h, int il) {
 int loaded_canonical(golhip_t h) {
     h->il = 0;
     h->loaded = true;
+    // a new board: the last batch's list sizes say nothing about its flip lists
+    h->ft_est = 0;
+    h->group_ft_est = 0;
     return set_layout(h, want_il(h));
 }
 

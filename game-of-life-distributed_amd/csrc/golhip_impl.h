@@ -232,6 +232,7 @@ struct golhip {
     gh::DevScratch<uint32_t> d_vcount;  // group view: count rows of the pixel rows that straddle strips
     bool flips_valid = false;
     int64_t flips_turn = -1;
+    bool flips_counted = false;   // d_blk and d_scalars[1] still hold the flip list's counts (golhip_alive_cells reuses them)
 
     // ring
     ncclComm_t comm = nullptr;

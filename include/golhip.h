@@ -27,6 +27,19 @@
  * driven by one engine thread; golhip_turn and golhip_alive_count may be
  * called concurrently from another thread (the reference's ticker, :283-302)
  * and return a (turn, count) pair that belongs together.
+ *
+ * The handle as a state machine: oracle/handle_model.py restates this header
+ * as a numpy model of one handle (and of a group of strips) -- the board, the
+ * turn, the flip list kept, the checkpoints and images in flight -- and
+ * answers every call with the value or the code documented here; where this
+ * header is silent the model says nothing.  tests/test_gpu_sequences.py draws
+ * seeded call sequences from the model's weighted tables (loads, stamps,
+ * steps, flip and view streams, plan changes between steps, observers, jobs
+ * in flight, refused calls) and compares handle and model after every call;
+ * its last test requires that the committed seeds took every kernel family
+ * (K1g, K1, K1w, the pair rule, K1r, K1p, the padded torus, K5, K5r), moved
+ * the words per lane of a loaded board up and down, and put a stamp, a clear
+ * and a step between a job's begin and its wait.
  */
 #ifndef GOLHIP_H
 #define GOLHIP_H
@@ -214,8 +227,9 @@ int golhip_set_option(golhip_t h, const char *key, int64_t value);
  * any-width kernel, by the board's cells and the turns of the call (DESIGN.md
  * 5.17), falling back to that kernel if the wide board cannot be allocated;
  * 0: never; 1: always (golhip_step then fails with GOLHIP_ENOMEM if the wide
- * board cannot be allocated) -- GOLHIP_EINVAL on a strip, a ring or a handle
- * whose width is a multiple of 32.  It concerns golhip_step alone (and what
+ * board cannot be allocated) -- mode 1 is GOLHIP_EINVAL on a strip, a ring or
+ * a handle whose width is a multiple of 32 (-1 and 0 are accepted there and
+ * change nothing).  It concerns golhip_step alone (and what
  * steps through it): golhip_flip_stream, golhip_step_flips and
  * golhip_group_flip_stream run every width on the fused turn + list kernel,
  * which closes the row seam itself (no wide board, pad_launches stays 0); the
@@ -328,7 +342,10 @@ int golhip_alive_count(golhip_t h, uint64_t *count, int64_t *at_turn);
 /* Sum over the RCCL ring (equals golhip_alive_count without a comm). */
 int golhip_alive_count_global(golhip_t h, uint64_t *count, int64_t *at_turn);
 /* Cells that changed in the last stepped turn (want_flips), row-major,
- * (x = col, y = row) pairs in global coordinates.  ERANGE sets *n. */
+ * (x = col, y = row) pairs in global coordinates.  ERANGE sets *n.  The list
+ * stays until the board is stepped, loaded, cleared or stamped: observers
+ * (counts, snapshots, golhip_alive_cells, frames, checkpoints) keep it.
+ * GOLHIP_EINVAL where the handle keeps no list of its current turn. */
 int golhip_flips(golhip_t h, int32_t *xy, uint64_t cap, uint64_t *n);
 /* Batched CellFlipped stream (distributor.go:93-173 with the per-turn
  * initializeAliveCells :212-220): advance nturns turns one at a time and
@@ -350,6 +367,11 @@ int golhip_step_flips(golhip_t h, int64_t nturns, int32_t *xy, uint64_t cap, uin
  * is left at the last turn that fitted, *turns_done says how many ran
  * (counts[t] for t < *turns_done), *n = entries written.  If not even the
  * first turn fits: GOLHIP_ERANGE, nothing advanced, *n = entries it needs.
+ * A batch may also stop short of a turn that would have fitted (it launches
+ * the turns the last batch's largest list says the buffer holds); where it
+ * does, a second call with the same buffer continues.  The first batch after
+ * the board was replaced (a load, fill, clear, checkpoint or image load) runs
+ * every turn that fits.
  * One host round trip per call.  Not for multi-rank rings (a stop on one
  * rank would desynchronise them): use golhip_step_flips there. */
 #define GOLHIP_FLIPS_XY 0

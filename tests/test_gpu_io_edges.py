@@ -308,9 +308,9 @@ def test_snapshot_rows_every_range(W, H, wpl, lanes):
 # ---------------------------------------------------------------- E: the flip list's contract
 @pytest.mark.parametrize("W,H,wpl", [(64, 64, 0), (100, 37, 0), (64, 64, 2)])
 def test_flip_list_validity(W, H, wpl):
-    """A flip list belongs to the turn that made it: a later step or an
-    alive_cells() (which reuses the block counts) retires it, the read-only
-    side channels do not."""
+    """A flip list belongs to the turn that made it: a later step retires it,
+    the read-only side channels do not -- nor does alive_cells(), which reuses
+    the block counts: flips() then counts again and still gives the turn's list."""
     board = random_board(W, H, 7 * W + H)
     boards = [board]
     for _ in range(6):
@@ -326,7 +326,7 @@ def test_flip_list_validity(W, H, wpl):
         assert_no_flip_list(b)  # never the list of turn 1 at turn 2
         b.step(1, want_flips=True)
         assert np.array_equal(b.alive_cells(), alive_cells_np(boards[3]))
-        assert_no_flip_list(b)  # not a list scanned for another input
+        assert np.array_equal(b.flips(), lists[2])  # not a list scanned for another input: the turn's own
         b.step(3, want_flips=True)
         assert np.array_equal(b.snapshot_bits(), pack_bits(boards[6]))
         assert np.array_equal(b.snapshot_rows(H // 3, H // 2), pack_bits(boards[6])[H // 3:H // 3 + H // 2])
