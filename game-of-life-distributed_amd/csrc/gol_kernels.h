@@ -81,6 +81,7 @@ struct SkewArgs {
     unsigned long long *trace;  // nullable diagnostics: per wave (start, end) s_memrealtime at 8 + 2 (block * 64 + wave),
                                 // (fill done, main loop done) at 8 + 2 (block * 64 + 8 + wave)
     int pairs;        // 1: the pair rule in the main loop (8 LUTs a word-turn; bands in multiples of 6 rows)
+    int interior;     // 1: the main loop's interior span runs its own body (gol_skew_span.h); 0: the general one throughout
 };
 bool skew_supported(int depth, int wpl, bool half = false, bool pr = false);
 int skew_blocks_per_cu(int depth, int wpl, bool half = false, bool pr = false);

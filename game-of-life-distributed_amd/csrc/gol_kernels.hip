@@ -16,6 +16,7 @@
 #include "gol_bits.h"
 #include "gol_layout.h"
 #include "gol_flip_seam.h"
+#include "gol_skew_span.h"
 
 #include <algorithm>
 #include <climits>
@@ -810,7 +811,7 @@ __device__ __forceinline__ void push_group_exp(Lanes<WPL> &x0, Lanes<WPL> &x1, L
 // more code (each phase is a loop of its own).
 template <int D>
 struct SkewPlan {
-    static constexpr int STEP = D > 20 ? 6 : 3;
+    static constexpr int STEP = skew_phase_step(D);
     static constexpr int NPH = (D - 1) / STEP;  // drain phases (also the fill phases before the full one)
     static constexpr int P(int j) { return (j + 1) * STEP; }
     static constexpr int NROWS(int j) { return 2 * ((j + 1 < NPH ? P(j + 1) : D) - P(j)); }
@@ -1084,7 +1085,7 @@ template <int D, int WPL, bool HALF = false, bool PR = false>
 __device__ __forceinline__ uint32_t stream_skew(const StepArgs &a, int ab, int eb, int tile, bool self,
                                                 uint32_t *exp_mine, const uint32_t *exp_next, int *flag_mine,
                                                 int *flag_next, unsigned *error, unsigned long long *phase_tr,
-                                                int dr = 0) {
+                                                int dr = 0, bool interior = false) {
     using SP = SkewPlan<D>;
     constexpr int ROW = 64 * WPL;  // words of one LDS row
     constexpr int TV = HALF ? kHalfTileValid : kTileValid;
@@ -1093,6 +1094,13 @@ __device__ __forceinline__ uint32_t stream_skew(const StepArgs &a, int ab, int e
     const int rofs = (HALF && lane >= 32) ? dr : 0;  // the upper half's rows
     const int Ww = a.Ww;
     const int S = eb - ab;
+    // the main loop's interior span (decided here, ahead of the pipeline state: its divisions take registers)
+    constexpr bool SPAN = skew_interior_instance(D, WPL, HALF, PR);
+    SkewSpan span = {0, 0};
+    if constexpr (SPAN)
+        span = skew_interior_span(SkewSpanIn{ab, eb, D, self, PR, a.in.off, a.in.wrap, a.in.rmax, HALF, dr, Ww,
+                                             a.alive != nullptr && a.count_lo < a.count_hi, interior});
+    const int k_in = __builtin_amdgcn_readfirstlane(span.k_lo), k_out = __builtin_amdgcn_readfirstlane(span.k_hi);
     const int t0 = tile * TV * WPL;
     int col = (t0 + WPL * (hl - 1)) % Ww;
     if (col < 0) col += Ww;
@@ -1197,24 +1205,96 @@ __device__ __forceinline__ uint32_t stream_skew(const StepArgs &a, int ab, int e
     [[maybe_unused]] PairSt<D, WPL> st;  // PR: the main loop's and the drain's stage state
     [[maybe_unused]] Shifted sh = {0u, 0u};  // PR: the lane shifts of the next group's first row
     // main: every stage on board rows (the bottom band of a stack to the end)
-    const int kmain = S + (self ? 2 * D : 2 * SP::P(0));
+    const int kmain = skew_main_end(S, D, self);
+    // The interior span (gol_skew_span.h): between its ends the row map neither
+    // wraps nor clamps, every stored row is inside the band and nothing is
+    // counted, so the bodies there load and store at a per-lane constant offset
+    // (the stores' halo lanes out of range) plus the row's scalar offset, which
+    // advances by a row's bytes and which the buffer does not range-check:
+    // the span alone keeps those stores inside the band.  The general loop runs
+    // up to the span and again from its end on.
+    const int kgen = k_in < k_out ? k_in : kmain;  // the general loop runs up to the span
+    const int ivoff = keep ? colw * 4 : INT_MAX;
+    // (buffer loads too: a per-lane 64-bit row pointer costs a VALU add a row
+    // and a hazard s_nop before the load that uses it)
+    __amdgpu_buffer_rsrc_t irs = brs;  // the span's input rows, from the first one on
+    int ilofs = 0;                   // the lane's byte offset in them (HALF: the upper lanes' rows too)
+    int iroff = 0;                   // byte offset of the next input row of the span
+    int isoff = 0;                   // byte offset of the next output row of the span from the band's first
+    [[maybe_unused]] auto iload = [&]() -> Lanes<WPL> {
+        Lanes<WPL> v;
+        if constexpr (WPL == 1) {
+            v.w[0] = __builtin_amdgcn_raw_buffer_load_b32(irs, ilofs, iroff, 0);
+        } else if constexpr (WPL == 2) {
+            const auto q = __builtin_amdgcn_raw_buffer_load_b64(irs, ilofs, iroff, 0);
+            v.w[0] = q[0];
+            v.w[1] = q[1];
+        } else {
+            const auto q = __builtin_amdgcn_raw_buffer_load_b128(irs, ilofs, iroff, 0);
+            v.w[0] = q[0];
+            v.w[1] = q[1];
+            v.w[2] = q[2];
+            v.w[3] = q[3];
+        }
+        iroff += Ww * 4;
+        return v;
+    };
+    [[maybe_unused]] auto istore = [&](const Lanes<WPL> &y) {
+        if constexpr (WPL == 1)
+            __builtin_amdgcn_raw_buffer_store_b32(y.w[0], brs, ivoff, isoff, GOL_SKEW_STORE_CPOL);
+        else if constexpr (WPL == 2)
+            __builtin_amdgcn_raw_buffer_store_b64((__attribute__((ext_vector_type(2))) unsigned){y.w[0], y.w[1]}, brs,
+                                                  ivoff, isoff, GOL_SKEW_STORE_CPOL);
+        else
+            __builtin_amdgcn_raw_buffer_store_b128(
+                (__attribute__((ext_vector_type(4))) unsigned){y.w[0], y.w[1], y.w[2], y.w[3]}, brs, ivoff, isoff,
+                GOL_SKEW_STORE_CPOL);
+        isoff += Ww * 4;
+    };
+    // entering the span at push k: the row cursor and the store offset of the general loop, as they stand
+    [[maybe_unused]] auto span_enter = [&]() {
+        // one base for the wave: the upper half's rows are ahead of the lower's or, once it has wrapped, behind
+        // them, by less than 2 GiB either way (the span is empty otherwise)
+        int rb = r;
+        if constexpr (HALF) rb = min(__builtin_amdgcn_readlane(r, 0), __builtin_amdgcn_readlane(r, 32));
+        irs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(a.src) + (size_t)(a.in.base + rb) * Ww, (short)0,
+                                                -1, 0x00020000);
+        ilofs = (col + (r - rb) * Ww) * 4;
+        iroff = 0;
+        isoff = (k - 3 - 2 * D) * Ww * 4;
+    };
+    // leaving it: the rows it loaded did not wrap, the next one may
+    [[maybe_unused]] auto span_leave = [&](int rows) {
+        r += rows;
+        if (r == wrap) r = 0;
+        qoi = k - 3 - 2 * D;
+    };
     for (int i = 0; i < GOL_LOOP_PAD; ++i) asm volatile("s_nop 0");
     if constexpr (PR) {
         // the pair rule, two groups a body: the fill leaves k at KSTART (= 0
         // mod 6), other bands are multiples of 6 rows (gol_skew_kernel), so
         // the loop ends exactly at kmain where a drain follows; a stack's
         // bottom band may run up to 5 rows past its end (masked stores)
-        constexpr int KSTART = 3 * ((2 * D + 2) / 3);
+        constexpr int KSTART = skew_main_start(D);
         static_assert(KSTART % 6 == 0, "the pair main loop starts at an even push");
         {
             pr_enter<D, 0, WPL>(h0, h1, cc, st);
             sh = row_shifts<WPL>(x0);  // the first unit's shifts; every later unit's ride on the unit before it
-            for (; k < kmain; k += 6) {
+            // one body: two groups (KQ 0, 1); IN: the span's loads and stores
+            auto body = [&](auto in_tag) {
+                constexpr bool IN = decltype(in_tag)::value;
                 {
-                    const Lanes<WPL> n0 = load_next(), n1 = load_next(), n2 = load_next();
-                    emit(q0, qoi);
-                    emit(q1, qoi + 1);
-                    emit(q2, qoi + 2);
+                    const Lanes<WPL> n0 = IN ? iload() : load_next(), n1 = IN ? iload() : load_next(),
+                                     n2 = IN ? iload() : load_next();
+                    if constexpr (IN) {
+                        istore(q0);
+                        istore(q1);
+                        istore(q2);
+                    } else {
+                        emit(q0, qoi);
+                        emit(q1, qoi + 1);
+                        emit(q2, qoi + 2);
+                    }
                     __builtin_amdgcn_sched_barrier(0);
                     Lanes<WPL> y0 = x0, y1 = x1, y2 = x2;
                     Lanes<WPL> xn;
@@ -1231,10 +1311,17 @@ __device__ __forceinline__ uint32_t stream_skew(const StepArgs &a, int ab, int e
                     x2 = vmov(n2);
                 }
                 {
-                    const Lanes<WPL> n0 = load_next(), n1 = load_next(), n2 = load_next();
-                    emit(q0, qoi);
-                    emit(q1, qoi + 1);
-                    emit(q2, qoi + 2);
+                    const Lanes<WPL> n0 = IN ? iload() : load_next(), n1 = IN ? iload() : load_next(),
+                                     n2 = IN ? iload() : load_next();
+                    if constexpr (IN) {
+                        istore(q0);
+                        istore(q1);
+                        istore(q2);
+                    } else {
+                        emit(q0, qoi);
+                        emit(q1, qoi + 1);
+                        emit(q2, qoi + 2);
+                    }
                     __builtin_amdgcn_sched_barrier(0);
                     Lanes<WPL> y0 = x0, y1 = x1, y2 = x2;
                     Lanes<WPL> xn;
@@ -1248,33 +1335,61 @@ __device__ __forceinline__ uint32_t stream_skew(const StepArgs &a, int ab, int e
                     x1 = vmov(n1);
                     x2 = vmov(n2);
                 }
+            };
+            // (three loops in a row: around two loops in one outer loop the register
+            // allocator keeps the pipeline state of each in registers of its own)
+            for (; k < kgen; k += 6) body(std::false_type());
+            if constexpr (SPAN) if (k_in < k_out) {
+                span_enter();
+                for (; k < k_out; k += 6) body(std::true_type());
+                span_leave(k_out - k_in);
+                for (; k < kmain; k += 6) body(std::false_type());
             }
             // the drain continues on the pair state (h0 / h1 / cc dead here)
             // where its phases are whole two-group bodies, else on the 9-LUT one
             if constexpr (D % 3 != 0) pr_leave<D, 0, WPL>(st, h0, h1, cc);
         }
     }
-    for (; !PR && k < kmain; k += 3) {
-        const Lanes<WPL> n0 = load_next(), n1 = load_next(), n2 = load_next();
-        emit(q0, qoi);
-        emit(q1, qoi + 1);
-        emit(q2, qoi + 2);
-        __builtin_amdgcn_sched_barrier(0);
-        Lanes<WPL> y0 = x0, y1 = x1, y2 = x2;
-        push_group<D, D, WPL>(y0, y1, y2, h0, h1, cc);
-        q0 = y0;
-        q1 = y1;
-        q2 = y2;
-        qoi = k - 2 * D;
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (GOL_SKEW_WAIT_TRACE) wt0 = __builtin_amdgcn_s_memrealtime();
-        x0 = vmov(n0);
-        x1 = vmov(n1);
-        x2 = vmov(n2);
-        if constexpr (GOL_SKEW_WAIT_TRACE) {
-            asm volatile("s_waitcnt vmcnt(3)" ::: "memory");  // the rows have landed
-            wmain += __builtin_amdgcn_s_memrealtime() - wt0;
-            ++nmain;
+    if constexpr (!PR) {
+        auto body = [&](auto in_tag) {
+            constexpr bool IN = decltype(in_tag)::value;
+            const Lanes<WPL> n0 = IN ? iload() : load_next(), n1 = IN ? iload() : load_next(),
+                             n2 = IN ? iload() : load_next();
+            if constexpr (IN) {
+                istore(q0);
+                istore(q1);
+                istore(q2);
+            } else {
+                emit(q0, qoi);
+                emit(q1, qoi + 1);
+                emit(q2, qoi + 2);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            Lanes<WPL> y0 = x0, y1 = x1, y2 = x2;
+            push_group<D, D, WPL>(y0, y1, y2, h0, h1, cc);
+            q0 = y0;
+            q1 = y1;
+            q2 = y2;
+            qoi = k - 2 * D;
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (GOL_SKEW_WAIT_TRACE) wt0 = __builtin_amdgcn_s_memrealtime();
+            x0 = vmov(n0);
+            x1 = vmov(n1);
+            x2 = vmov(n2);
+            if constexpr (GOL_SKEW_WAIT_TRACE) {
+                asm volatile("s_waitcnt vmcnt(3)" ::: "memory");  // the rows have landed
+                wmain += __builtin_amdgcn_s_memrealtime() - wt0;
+                ++nmain;
+            }
+        };
+        // (three loops in a row: around two loops in one outer loop the register
+        // allocator keeps the pipeline state of each in registers of its own)
+        for (; k < kgen; k += 3) body(std::false_type());
+        if constexpr (SPAN) if (k_in < k_out) {
+            span_enter();
+            for (; k < k_out; k += 3) body(std::true_type());
+            span_leave(k_out - k_in);
+            for (; k < kmain; k += 3) body(std::false_type());
         }
     }
     if constexpr (GOL_SKEW_WAIT_TRACE) {
@@ -1433,6 +1548,7 @@ __global__ __launch_bounds__(512) void gol_skew_kernel(SkewArgs p) {
     // band boundaries at multiples of 3 rows from the stack start (drain
     // groups aligned with the drain phases, SkewPlan; 6 for the pair rule's
     // two-group main-loop body); the bottom band takes the rest
+    // (gol_skew_span.h skew_band restates this for the host)
     constexpr int G = PR ? 6 : 3;
     const int ab = A0 + (int)(Ls * cum / tot) / G * G;
     const int eb = bottom ? E0 : A0 + (int)(Ls * (cum + p.wgt[pos]) / tot) / G * G;
@@ -1441,7 +1557,7 @@ __global__ __launch_bounds__(512) void gol_skew_kernel(SkewArgs p) {
                                              &s_flag[w], bottom ? nullptr : &s_flag[w + p.tx], p.error,
                                              (p.trace && blockIdx.x < 1024) ? p.trace + 8 + 2 * (blockIdx.x * 64 + 16 + w)
                                                                             : nullptr,
-                                             L);
+                                             L, p.interior != 0);
     if (p.trace && lane == 0 && blockIdx.x < 1024) {
         p.trace[8 + 2 * (blockIdx.x * 64 + w)] = (unsigned long long)t_start;
         p.trace[8 + 2 * (blockIdx.x * 64 + w) + 1] = (unsigned long long)__builtin_amdgcn_s_memrealtime();

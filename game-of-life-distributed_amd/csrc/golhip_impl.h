@@ -157,6 +157,7 @@ struct golhip {
     int lds_bpc_stride[4] = {};
     int skew_bpc[gh::kNumDepths][12] = {};  // K1w workgroups per CU by (depth, wpl, half, pairs) (0: not queried)
     int skew_pairs = 5;             // option "skew_pairs": the pair rule (8 LUTs a word-turn) at depth 18 (depth_cap)
+    int skew_interior = 1;          // option "skew_interior": K1w's interior main-loop body (gol_skew_span.h; 0: the general body alone)
     unsigned *skew_err = nullptr;      // host-mapped spin-bound flag of the K1w kernels
     unsigned *skew_err_dev = nullptr;
     int lds_band = -1;              // option "lds_band": resident LDS bands K1r (1 on where it fits, 0 off, -1 auto)

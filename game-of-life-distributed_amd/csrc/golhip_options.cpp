@@ -34,7 +34,10 @@ namespace {
 
 // Who may set an option: anyone (product), or a caller whose environment
 // consents to A/B tuning knobs, to wrong results, to test hooks (above).
-enum Consent : unsigned { kProduct = 1, kTuning = 2, kMeasurement = 4, kTestHook = 8 };
+// kPathSwitch: a tuning knob that only picks between two code paths of one
+// plan (same launches, same results); it needs the tuning consent too, but
+// golhip_build_info()'s CONSENT_TUNING names the knobs of the plans alone.
+enum Consent : unsigned { kProduct = 1, kTuning = 2, kMeasurement = 4, kTestHook = 8, kPathSwitch = 16 };
 
 constexpr int64_t kAny = INT64_MAX;  // lo = -kAny, hi = kAny: every value
 
@@ -130,6 +133,8 @@ constexpr Option kOptions[] = {
     {"lds_xcd", kTuning, RANGE(0, 1), &golhip::lds_xcd, false, false, nullptr},
     {"flip_overlap", kTuning, RANGE(0, 3), &golhip::flip_overlap, false, false, nullptr},
     {"skew_pairs", kTuning, RANGE(0, 7), &golhip::skew_pairs, false, false, nullptr},
+    // K1w's interior main-loop body (gol_skew_span.h); 0: an empty span, the general body alone
+    {"skew_interior", kPathSwitch, RANGE(0, 1), &golhip::skew_interior, false, false, nullptr},
     // measurement only: the halo rows go stale (wrong results)
     {"halo_skip", kMeasurement, BOOLEAN, &golhip::halo_skip, true, false, nullptr},
     {"resident_fault", kTestHook, RANGE(0, 2), &golhip::resident_fault, false, false, nullptr},
@@ -218,7 +223,7 @@ int golhip_set_option(golhip_t h, const char *key, int64_t value) {
     if (int rc = check(h)) return rc;
     if (!key) return fail(GOLHIP_EINVAL, "null option");
     const Option *o = find_option(key);
-    if (o && (o->consent & kTuning) && !tuning_env())
+    if (o && (o->consent & (kTuning | kPathSwitch)) && !tuning_env())
         return fail(GOLHIP_EINVAL, "%s is an A/B tuning knob of the kernel plans: set GOLHIP_TUNING=1", key);
     std::lock_guard<std::mutex> g(h->mu);
     if (!o) return fail(GOLHIP_EINVAL, "unknown option %s", key);

@@ -109,6 +109,7 @@ static void take_settings(golhip_t h, golhip *w) {
     w->skew_tx = h->skew_tx;
     w->skew_half = h->skew_half;
     w->skew_pairs = h->skew_pairs;
+    w->skew_interior = h->skew_interior;
     w->d_trace = h->d_trace;
 }
 

@@ -2,6 +2,7 @@
 // launch, words per lane, band and stack shapes.  Decisions on plain integers
 // plus occupancy queries cached in the handle; nothing is launched here.
 #include "golhip_impl.h"
+#include "gol_skew_span.h"
 #include <climits>
 #include <functional>
 
@@ -311,6 +312,7 @@ bool skew_dims(golhip_t h, int depth, int wpl, int L, golk::SkewArgs *sk) {
     if (!best_tx) return false;
     sk->tiles_x = best_tiles;
     sk->pairs = pr ? 1 : 0;
+    sk->interior = h->skew_interior && golk::skew_interior_instance(depth, wpl, best_half != 0, pr);
     sk->tx = best_tx;
     sk->nst = best_nst;
     sk->half = best_half;
@@ -486,6 +488,49 @@ int golhip_halo_schedule(int32_t strip_rows, int32_t tb_depth, int32_t resident,
     const HaloRun hr = halo_next(std::min(tb_depth, strip_rows), strip_rows, resident != 0, turns_left);
     *depth = hr.d;
     *launches = hr.k;
+    return GOLHIP_OK;
+}
+
+int golhip_skew_span(const golhip_skew_span_in_t *in, int32_t *k_lo, int32_t *k_hi) {
+    if (!in || !k_lo || !k_hi || in->depth < 4 || in->depth > GOLHIP_MAX_TB_DEPTH || in->eb < in->ab || in->dr < 0 || in->row_words < 1)
+        return fail(GOLHIP_EINVAL, "bad skew span request");
+    const golk::SkewSpan s = golk::skew_interior_span(golk::SkewSpanIn{
+        in->ab, in->eb, in->depth, in->self != 0, in->pair != 0, in->off, in->wrap, in->rmax, in->half != 0, in->dr, in->row_words,
+        in->counts != 0, in->enabled != 0});
+    *k_lo = s.k_lo;
+    *k_hi = s.k_hi;
+    return GOLHIP_OK;
+}
+
+int golhip_skew_interior_plan(golhip_t h, int32_t depth, int32_t ext, int32_t counts, int64_t *interior_bodies,
+                              int64_t *main_bodies) {
+    if (int rc = check(h)) return rc;
+    if (!interior_bodies || !main_bodies || depth < 1 || ext < 0) return fail(GOLHIP_EINVAL, "bad skew interior request");
+    std::lock_guard<std::mutex> g(h->mu);
+    *interior_bodies = *main_bodies = 0;
+    const bool halo = h->halo_mode();
+    if (ext > 0 && !halo) return fail(GOLHIP_EINVAL, "extended rows: strips only");
+    golk::StepArgs a = step_args(h, nullptr, halo);
+    if (ext > 0) {  // launch_rows' deep-halo extension
+        a.rows_out = h->rows + 2 * ext;
+        a.in.off = kHalo - ext;
+        a.count_lo = ext;
+        a.count_hi = ext + h->rows;
+    }
+    golk::SkewArgs sk{};
+    const int wpl = wpl_for(h);
+    if (!skew_plan(h, depth, wpl, a, &sk)) return GOLHIP_OK;  // no K1w launch at this depth: no bodies
+    const int sy = 8 / sk.tx, L = sk.half ? a.rows_out / 2 : a.rows_out, B = sk.pairs ? 6 : 3;
+    for (int stack = 0; stack < sk.nst; ++stack)
+        for (int pos = 0; pos < sy; ++pos) {
+            const golk::SkewBand b = golk::skew_band(L, sk.nst, stack, sy, pos, sk.wgt, sk.hcap, depth, sk.pairs != 0);
+            const golk::SkewSpan s = golk::skew_interior_span(golk::SkewSpanIn{
+                b.ab, b.eb, depth, b.bottom, sk.pairs != 0, a.in.off, a.in.wrap, a.in.rmax, sk.half != 0, L, a.Ww,
+                counts != 0 && a.count_lo < a.count_hi, sk.interior != 0});
+            const int k0 = golk::skew_main_start(depth), k1 = golk::skew_main_end(b.eb - b.ab, depth, b.bottom);
+            *interior_bodies += (int64_t)(s.k_hi - s.k_lo) / B * sk.tiles_x;
+            *main_bodies += (int64_t)(std::max(k1 - k0, 0) + B - 1) / B * sk.tiles_x;
+        }
     return GOLHIP_OK;
 }
 

@@ -192,7 +192,11 @@ int golhip_set_rows_per_wave(golhip_t h, int32_t rows);
  * lds_age, lds_pre, lds_stride, lds_xcd, skew_pairs (bit 1: tori and strips on
  * full-width K1w tiles run 18 turns a launch with the pair rule, 8 LUTs a
  * word-turn; bit 4: half-wave tile plans too; bit 2: quads at 8 on the pair
- * rule; default 5),
+ * rule; default 5), skew_interior (1, the default: that kernel's main loop
+ * runs the rows between a band's first and last stored rows, where the row map
+ * neither wraps nor clamps, through a body without the per-row decisions, in
+ * launches that count nothing; 0: the general body throughout; same results,
+ * DESIGN.md 5.20; not listed by golhip_build_info()),
  * flip_overlap (how a golhip_flip_stream into golhip_host_alloc memory
  * delivers the lists: 2 (the default), boards of at least 64 K words run the
  * batch's turns as one resident launch whose copy blocks move each turn's
@@ -316,6 +320,29 @@ int golhip_halo_plan(int32_t width, int32_t strip_rows, int32_t nranks, int32_t 
  * full-depth super-steps greedily instead of the balanced launch plan. */
 int golhip_halo_schedule(int32_t strip_rows, int32_t tb_depth, int32_t resident, int64_t turns_left,
                          int32_t *depth, int32_t *launches);
+/* The interior span of one band of a skewed-stack launch (exposed for tests;
+ * DESIGN.md 5.20): the main-loop pushes [k_lo, k_hi), whole loop bodies, in
+ * which the band's input rows [ab, eb) neither wrap (wrap; 0: no wrap) nor
+ * clamp (rmax) through the row map (off), every stored row lies inside the
+ * band and nothing is counted, exactly as the kernel decides it.  self: the
+ * stack's bottom band; pair: the pair rule's bodies of six rows (else three);
+ * half: the wave's upper lanes run the same band dr rows further down (both
+ * halves within 2 GiB of one base, at row_words words a row); counts:
+ * the launch counts alive cells; enabled: option "skew_interior".  Empty
+ * (k_lo = k_hi) when there is none. */
+typedef struct golhip_skew_span_in {
+    int32_t ab, eb, depth, self, pair;
+    int32_t off, wrap, rmax;
+    int32_t half, dr, row_words, counts, enabled;
+} golhip_skew_span_in_t;
+int golhip_skew_span(const golhip_skew_span_in_t *in, int32_t *k_lo, int32_t *k_hi);
+/* The same over every wave of the skewed-stack launch of `depth` turns this
+ * handle would run now (a strip: over its rows extended by ext on either
+ * side; counts != 0: a launch that counts): main-loop bodies inside an
+ * interior span, and all main-loop bodies.  Both 0 where no such launch
+ * exists at that depth. */
+int golhip_skew_interior_plan(golhip_t h, int32_t depth, int32_t ext, int32_t counts, int64_t *interior_bodies,
+                              int64_t *main_bodies);
 
 /* ---- board I/O -------------------------------------------------------- */
 /* Load this handle's rows (height x width bytes, or its strip's rows). */

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e_)); exit(1); } } while (0)
 
@@ -169,6 +170,47 @@ KERNEL(k_pr_gap4, P_pr_gap4)
     B3(42,50,51,52) DPP(46,62) B3(43,51,52,53) B3(40,52,53,54) B3(41,53,54,55) B3(42,54,55,56) B3(43,55,56,57) ALB(47,63,46)
 KERNEL(k_pr_gap3_5, P_pr_gap3_5)
 
+// One body of the pair main loop of gol_skew_kernel<18, 2, false, true>
+// (DESIGN.md §5.20): two 3-row groups of 27 pr_gap3_5 units (2,160 rule
+// instructions) with the body's other instructions in their classes and
+// places, the loads, stores and waits left out (no memory traffic here; both
+// bodies have the same 6 + 6 + 6).  body_general: per group 52 SALU (row
+// clamp, wrap select, 64-bit row offset, store and count range masks) and 21
+// VALU (load address, store offset select and adds, popcounts, count select)
+// ahead of the group, the six row moves at its end.  body_interior: 10 SALU
+// (the rows' scalar offsets) ahead of the group and the same six moves.  One
+// copy of the body per loop trip (.rept 1): 18 KB of code, as in the kernel.
+#define SROW "s_min_i32 s22, s20, s21\ns_add_i32 s22, s22, s23\ns_mul_hi_i32 s25, s22, s21\ns_mul_i32 s24, s22, s21\n" \
+             "v_lshl_add_u64 v[58:59], s[24:25], 2, v[60:61]\ns_add_i32 s20, s20, 1\ns_cmp_lg_u32 s20, s23\ns_cselect_b32 s20, s20, 0\n"
+#define SSTORE "s_cmp_lt_u32 s22, s21\ns_cselect_b64 s[26:27], s[28:29], 0\ns_cmp_ge_i32 s22, s23\ns_cselect_b64 s[24:25], -1, 0\n" \
+               "s_cmp_lt_i32 s22, s21\ns_cselect_b64 vcc, -1, 0\nv_cndmask_b32 v57, v62, v63, vcc\nv_add_u32 v56, v57, v56\nv_add_u32 v57, v56, v57\n" \
+               "v_bcnt_u32_b32 v58, v48, 0\ns_and_b64 s[24:25], s[26:27], s[24:25]\nv_bcnt_u32_b32 v58, v49, v58\ns_and_b64 vcc, vcc, s[24:25]\n" \
+               "v_cndmask_b32 v59, 0, v58, vcc\n"
+#define SMISC "s_add_i32 s22, s22, 3\ns_sub_i32 s23, s23, s21\ns_add_i32 s20, s20, s21\ns_sub_i32 s22, s22, 1\ns_add_i32 s23, s23, 2\ns_add_i32 s22, s22, s23\ns_add_i32 s23, s23, s21\n"
+#define HEAD_GENERAL SMISC SROW SROW SROW SSTORE SSTORE SSTORE "s_nop 0\ns_nop 0\n"
+#define SOFF "s_add_i32 s22, s20, s21\n"
+#define HEAD_INTERIOR SOFF SOFF SOFF SOFF SOFF SOFF SOFF "s_add_i32 s20, s20, 6\ns_add_i32 s21, s21, s23\ns_cmp_lt_i32 s20, s23\n" "s_nop 0\ns_nop 0\n"
+#define MOV2 "v_mov_b32 v52, v62\nv_mov_b32 v53, v63\n"
+#define MOV4 "v_mov_b32 v54, v62\nv_mov_b32 v55, v63\nv_mov_b32 v56, v62\nv_mov_b32 v57, v63\n"
+#define U1 P_pr_gap3_5
+#define U5 U1 U1 U1 U1 U1
+#define U26 U5 U5 U5 U5 U5 U1
+#define P_body_general HEAD_GENERAL U26 MOV2 U1 MOV4 HEAD_GENERAL U26 MOV2 U1 MOV4
+#define P_body_interior HEAD_INTERIOR U26 MOV2 U1 MOV4 HEAD_INTERIOR U26 MOV2 U1 MOV4
+#define P_body_rule U26 U1 U26 U1
+#define SCLOB "s20", "s21", "s22", "s23", "s24", "s25", "s26", "s27", "s28", "s29", "vcc", "scc"
+#define KERNEL1(name, body)                                                       \
+    constexpr int name##_n = nlines(body);                                        \
+    __global__ void name(int iters, long long* sink) {                           \
+        const long long c0 = clock64(), w0 = wall_clock64();                      \
+        for (int i = 0; i < 16 * iters; ++i) asm volatile(body ::: CLOB, SCLOB);  \
+        const long long c1 = clock64(), w1 = wall_clock64();                      \
+        if (threadIdx.x == 0) { sink[2 * blockIdx.x] = c1 - c0; sink[2 * blockIdx.x + 1] = w1 - w0; } \
+    }
+KERNEL1(k_body_rule, P_body_rule)
+KERNEL1(k_body_general, P_body_general)
+KERNEL1(k_body_interior, P_body_interior)
+
 typedef void (*kfn)(int, long long*);
 
 int main(int argc, char** argv) {
@@ -183,12 +225,16 @@ int main(int argc, char** argv) {
         {"chain1", k_chain1, k_chain1_n}, {"chain2", k_chain2, k_chain2_n}, {"chain4", k_chain4, k_chain4_n}, {"dpp", k_dpp, k_dpp_n}, {"alignbit", k_alb, k_alb_n}, {"mix6:1:1", k_mix, k_mix_n}, {"mix9:1:1", k_mix911, k_mix911_n}, {"mix10:1:1", k_mix10, k_mix10_n},
         {"b3x15+dpp", k_d1, k_d1_n}, {"b3x15+alb", k_a1, k_a1_n}, {"b3x12+dpp4spread", k_d4s, k_d4s_n}, {"b3x12+alb4spread", k_a4s, k_a4s_n}, {"b3x12+dpp4grouped", k_d4g, k_d4g_n},
         {"b3x12+alb4grouped", k_a4g, k_a4g_n}, {"xor_vop2", k_xor, k_xor_n}, {"real_HHHVVH", k_real_HHHVVH, k_real_HHHVVH_n}, {"real_spread", k_real_spread, k_real_spread_n}, {"HH_pairs", k_HH_pairs, k_HH_pairs_n}, {"HV_alt", k_HV_alt, k_HV_alt_n}, {"HVV", k_HVV, k_HVV_n}, {"HVVV", k_HVVV, k_HVVV_n}, {"bperm_alb", k_bperm_alb, k_bperm_alb_n}, {"bperm2_alb2", k_bperm2_alb2, k_bperm2_alb2_n}, {"dpp_alb", k_dpp_alb, k_dpp_alb_n}, {"dpp2_alb2", k_dpp2_alb2, k_dpp2_alb2_n}, {"xor_e64", k_xor_e64, k_xor_e64_n}, {"xor3", k_xor3, k_xor3_n},
-        {"pr_grouped", k_pr_grouped, k_pr_grouped_n}, {"pr_gap2", k_pr_gap2, k_pr_gap2_n}, {"pr_gap3", k_pr_gap3, k_pr_gap3_n}, {"pr_gap4", k_pr_gap4, k_pr_gap4_n}, {"pr_gap3_5", k_pr_gap3_5, k_pr_gap3_5_n}};
+        {"pr_grouped", k_pr_grouped, k_pr_grouped_n}, {"pr_gap2", k_pr_gap2, k_pr_gap2_n}, {"pr_gap3", k_pr_gap3, k_pr_gap3_n}, {"pr_gap4", k_pr_gap4, k_pr_gap4_n}, {"pr_gap3_5", k_pr_gap3_5, k_pr_gap3_5_n},
+        {"body_rule", k_body_rule, k_body_rule_n}, {"body_general", k_body_general, k_body_general_n},
+        {"body_interior", k_body_interior, k_body_interior_n}};
+    const char* only = argc > 2 ? argv[2] : nullptr;  // a variant name prefix: run those alone
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));
     for (int wps : {1, 2, 4}) {
         for (auto& k : ks) {
+            if (only && strncmp(k.n, only, strlen(only)) != 0) continue;
             const int threads = 64 * 4 * wps;  // wps waves per SIMD, one workgroup per CU
             hipLaunchKernelGGL(k.f, dim3(cus), dim3(threads), 0, 0, 10, sink);
             CK(hipEventRecord(e0));
