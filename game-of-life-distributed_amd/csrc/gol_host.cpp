@@ -181,6 +181,7 @@ struct Engine {
             hs.push_back(nullptr);
             row0.push_back(0);
             check(golhip_create((int32_t)w, (int32_t)hgt, opt.device, 0, &hs[0]));
+            set_rule(opt);
             return;
         }
         int32_t ndev = 0;
@@ -199,6 +200,11 @@ struct Engine {
             hs.push_back(h);
             row0.push_back(r0);
         }
+        set_rule(opt);
+    }
+    // RunOptions::rule on every handle, before a board is there
+    void set_rule(const RunOptions &opt) {
+        for (golhip_t h : hs) check(golhip_set_rule(h, opt.rule.birth, opt.rule.survive));
     }
     ~Engine() {
         if (ckpt) golhip_checkpoint_wait(ckpt, nullptr);
@@ -321,10 +327,25 @@ void Run(Params p, Chan<Event> *events, Chan<char32_t> *keyPresses, const RunOpt
     if (!opt.resume_path.empty() && (opt.blank || !opt.patterns.empty()))
         throw std::runtime_error("resume: a run from a checkpoint takes neither blank nor patterns (a restarted job "
                                  "must not stamp twice)");
+    if (opt.rule.birth > 0x1FF || opt.rule.survive > 0x1FF) throw std::runtime_error("rule masks above 0x1FF");
+    const bool conway = opt.rule.birth == 0x008 && opt.rule.survive == 0x00C;
     // every pattern file's checks before a device is touched (golhip_pattern_info needs none)
     for (const RunOptions::Pattern &ps : opt.patterns) {
-        golhip_pattern_info_t pi;
-        if (golhip_pattern_info(ps.path.c_str(), &pi) != GOLHIP_OK) throw std::runtime_error(golhip_last_error());
+        golhip_pattern_info_t pi{};
+        if (!conway) {
+            // golhip_pattern_info takes Conway's files alone: a run on another rule checks the file's
+            // rule here (its own or none; an explicit B3/S23, and the size, are golhip_stamp_file's to refuse)
+            uint32_t fb = 0, fs = 0;
+            if (golhip_pattern_rule(ps.path.c_str(), &fb, &fs) != GOLHIP_OK) throw std::runtime_error(golhip_last_error());
+            if (!(fb == opt.rule.birth && fs == opt.rule.survive) && !(fb == 0x008 && fs == 0x00C)) {
+                char file_rule[32] = "", run_rule[32] = "";
+                golhip_rule_format(fb, fs, file_rule, sizeof file_rule);
+                golhip_rule_format(opt.rule.birth, opt.rule.survive, run_rule, sizeof run_rule);
+                throw std::runtime_error("RLE: rule " + std::string(file_rule) + " is not the board's " + run_rule);
+            }
+        } else if (golhip_pattern_info(ps.path.c_str(), &pi) != GOLHIP_OK) {
+            throw std::runtime_error(golhip_last_error());
+        }
         if (pi.width > W || pi.height > H)
             throw std::runtime_error("pattern " + ps.path + " is " + std::to_string(pi.width) + " x " +
                                      std::to_string(pi.height) + ": it does not fit the " + name + " board");
@@ -893,6 +914,11 @@ int golrun_start_opts(int64_t turns, int64_t threads, int64_t width, int64_t hei
     if (opts->reserved[1] != 0) o.stream_images = 1;
     o.image_every = opts->reserved[0];
     o.blank = opts->reserved[3] != 0;
+    if (opts->reserved0 != 0) {  // the rule: 0x40000 | survive << 9 | birth
+        if ((opts->reserved0 & ~0x7FFFF) != 0 || !(opts->reserved0 & 0x40000)) return run_fail("bad rule word in reserved0");
+        o.rule.birth = (uint32_t)opts->reserved0 & 0x1FF;
+        o.rule.survive = ((uint32_t)opts->reserved0 >> 9) & 0x1FF;
+    }
     if (opts->reserved[2]) {  // one "path@x,y[,op]" a line
         std::stringstream lines(reinterpret_cast<const char *>((uintptr_t)opts->reserved[2]));
         try {

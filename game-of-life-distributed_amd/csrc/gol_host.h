@@ -455,6 +455,15 @@ struct RunOptions {
     };
     bool blank = false;
     std::vector<Pattern> patterns;
+    // The Life-like rule of the run (golhip_set_rule; masks as in golhip.h,
+    // Conway's by default): set on every handle, strips included, before the
+    // initial board's events.  With cell events the batches go through the
+    // flip streams as ever, which take one turn and one compaction a turn on
+    // another rule than Conway's.  A checkpoint keeps no rule: a run from
+    // resume_path names it again.  Pattern files: of this rule, or of none.
+    struct Rule {
+        uint32_t birth = 0x008, survive = 0x00C;
+    } rule;
 };
 
 // One "path@x,y[,op]" (op: copy | or | xor | clear, default or), as the

@@ -9,8 +9,9 @@
 // (dead), o (alive), $ (end of row) and ! (end of pattern), a missing count
 // meaning 1.  White space, line breaks included, may stand anywhere between
 // the body's characters, inside a run count too.  Trailing dead cells of a
-// row and trailing rows may be left out.  Only Conway's rule is accepted:
-// B3/S23 in either letter case, 23/3, or no rule at all.
+// row and trailing rows may be left out.  Without a RuleMode only Conway's
+// rule is accepted: B3/S23 in either letter case, 23/3, or no rule at all; a
+// RuleMode accepts one other rule instead, or reports whichever the file names.
 // A pattern comes out as canonical bit words: ceil(width / 32) uint32 a row,
 // cell (y, x) = bit x % 32 of word x / 32, padding bits zero.
 #pragma once
@@ -22,10 +23,21 @@
 #include <vector>
 
 #include "gol_image_file.h"
+#include "gol_rule_text.h"
 
 namespace golpat {
 
 constexpr int kFormatRle = 0, kFormatPgm = 1;
+
+// What a file's "rule =" field is held against: kAccept, the rule (birth,
+// survive) or none; kReport, any rule golrule::parse takes.  Either way the
+// file's rule comes back in (found_birth, found_survive), Conway's where it
+// names none (a PGM never does).
+struct RuleMode {
+    enum Kind { kAccept, kReport } kind = kReport;
+    uint32_t birth = golrule::kConwayBirth, survive = golrule::kConwaySurvive;
+    uint32_t found_birth = golrule::kConwayBirth, found_survive = golrule::kConwaySurvive;
+};
 
 struct Info {
     int64_t width = 0, height = 0;
@@ -38,7 +50,7 @@ inline bool is_pgm(const unsigned char *bytes, size_t have) { return have >= 2 &
 
 // The header of RLE text: skips '#' lines and blank lines, reads "x = m, y = n
 // [, rule = r]", checks size and rule.  *body: offset of the first body byte.
-inline bool rle_header(const char *t, size_t n, Info *info, size_t *body, std::string *why) {
+inline bool rle_header(const char *t, size_t n, Info *info, size_t *body, std::string *why, RuleMode *rm = nullptr) {
     size_t pos = 0;
     auto line_end = [&](size_t p) {
         while (p < n && t[p] != '\n') ++p;
@@ -87,7 +99,18 @@ inline bool rle_header(const char *t, size_t n, Info *info, size_t *body, std::s
         *why = "RLE: no header line \"x = m, y = n[, rule = r]\"";
         return false;
     }
-    if (!rule.empty()) {
+    if (!rule.empty() && rm) {
+        std::string perr;
+        if (!golrule::parse(rule.c_str(), &rm->found_birth, &rm->found_survive, &perr)) {
+            *why = "RLE: " + perr;
+            return false;
+        }
+        if (rm->kind == RuleMode::kAccept && (rm->found_birth != rm->birth || rm->found_survive != rm->survive)) {
+            *why = "RLE: rule " + golrule::format(rm->found_birth, rm->found_survive) + " is not the board's " +
+                   golrule::format(rm->birth, rm->survive);
+            return false;
+        }
+    } else if (!rule.empty()) {
         std::string up;
         for (char c : rule) up.push_back((char)std::toupper((unsigned char)c));
         if (up != "B3/S23" && up != "23/3") {
@@ -191,7 +214,8 @@ inline bool slurp(const char *path, std::string *out, std::string *why) {
 // cap_words before anything is read into `words`, and `fits` (nullable) may
 // refuse a size first (a pattern larger than the board it is meant for).
 template <typename Fits>
-inline int read(const char *path, uint32_t *words, uint64_t cap_words, Info *info, std::string *why, Fits &&fits) {
+inline int read(const char *path, uint32_t *words, uint64_t cap_words, Info *info, std::string *why, Fits &&fits,
+                RuleMode *rm = nullptr) {
     unsigned char magic[2] = {0, 0};
     {
         std::FILE *f = std::fopen(path, "rb");
@@ -241,7 +265,7 @@ inline int read(const char *path, uint32_t *words, uint64_t cap_words, Info *inf
     std::string text;
     if (!slurp(path, &text, why)) return 1;
     size_t body = 0;
-    if (!rle_header(text.data(), text.size(), info, &body, why)) return 1;
+    if (!rle_header(text.data(), text.size(), info, &body, why, rm)) return 1;
     if (!fits(*info, why)) return 1;
     if (!words) return rle_body(text.data(), text.size(), body, info, why, [](int64_t, int64_t, int64_t) {}) ? 0 : 1;
     if (info->words() > cap_words) return 2;

@@ -75,9 +75,10 @@ struct FlipBatch {
     golk::StepArgs sa;
 };
 
-// Giant strips (2^32 - 4096 words or more, past K5's 32-bit word index): the
-// any-width kernel and the three-pass compaction one turn at a time, checked
-// on the host after each turn.
+// Giant strips (2^32 - 4096 words or more, past K5's 32-bit word index) and
+// handles with another rule than Conway's (K5 / K5r are B3/S23): one
+// per-launch turn and the three-pass compaction at a time, checked on the
+// host after each turn.
 static int flip_generic(golhip_t h, FlipBatch &b, int64_t *done_out, uint64_t *total_out) {
     const int64_t nw = b.nw, nturns = b.nturns;
     const uint64_t dcap = b.dcap;
@@ -278,7 +279,7 @@ static int flip_stream_locked(golhip_t h, int64_t nturns, int format, void *out,
     const int64_t t0 = h->turns;
     const int c0 = h->cur;
 
-    if (nw >= (1ll << 32) - 4096) return flip_generic(h, b, done_out, total_out);
+    if (nw >= (1ll << 32) - 4096 || h->rule_path()) return flip_generic(h, b, done_out, total_out);
 
     // fused turn + list (K5) on the canonical layout, at any width (W % 32 != 0:
     // the kernel closes the row seam itself, no padded torus); into a golhip_host_alloc
@@ -419,7 +420,8 @@ static int group_sync(golhip_t *hs, int n) {
     return GOLHIP_OK;
 }
 
-// Giant strips (2^32 - 4096 words or more): one group turn at a time through
+// Giant strips (2^32 - 4096 words or more) and groups with another rule than
+// Conway's: one group turn at a time through
 // the three-pass compaction, the board's count checked on the host before the
 // turn's entries are fetched (two synchronisations a turn); a turn that does
 // not fit is undone on every strip (its source board is still the other buffer).
@@ -737,7 +739,7 @@ int golhip_group_flip_stream(golhip_t *hs, int32_t n, int64_t nturns, int32_t fo
             return fail(GOLHIP_EINVAL, "strip %d is at turn %lld, strip 0 at turn %lld", i, (long long)hs[i]->turns,
                         (long long)hs[0]->turns);
         if (want_il(hs[i]) != want_il(hs[0])) return fail(GOLHIP_EINVAL, "strip %d uses another word layout", i);
-        fused &= hs[i]->local_words() < (1ll << 32) - 4096;
+        fused &= hs[i]->local_words() < (1ll << 32) - 4096 && !hs[i]->rule_path();
     }
     if (nturns == 0) return GOLHIP_OK;
     // group_exchange's events, made once for the call

@@ -568,7 +568,7 @@ int golhip_perf(golhip_t h, golhip_perf_t *out) {
         h->ms.step += h->wide->ms.step;
         h->wide->ms = Millis{};
     }
-    memset(out, 0, sizeof *out);  // (reserved2: a retired kernel family (round 5), kept for the ABI)
+    memset(out, 0, sizeof *out);
     const Counters &n = h->n;
     out->turns = h->turns;
     out->step_launches = n.step_launches;
@@ -600,6 +600,7 @@ int golhip_perf(golhip_t h, golhip_perf_t *out) {
     out->view_frames = n.view_frames;
     out->view_kernel_ms = h->ms.view;
     out->pad_launches = n.pad_launches;
+    out->rule_launches = n.rule_launches;
     out->words_per_lane = h->W % 32 == 0 ? wpl_for(h) : 0;
     out->persist_depth = h->W % 32 == 0 ? persist_depth_for(h, wpl_for(h)) : 0;
     return GOLHIP_OK;

@@ -22,6 +22,7 @@
 //   golhip_ckpt.cpp     checkpoints: shadow copy (K8), drain to a file, verified load
 //   golhip_image.cpp    PGM images: the same shadow copy, expanded to bytes in page-locked memory (K9), streamed load
 //   golhip_stamp.cpp    patterns: an empty board, a rectangle of cells stamped on the torus (K10), pattern files
+//   golhip_rule.cpp     Life-like rules: their spelling, golhip_set_rule
 //   golhip_pad.cpp      the padded torus and padded strips: widths that are no multiple of 32 on the fast kernels
 //
 // Everything here but `struct golhip` lives in namespace gh, whose symbols
@@ -43,6 +44,7 @@
 
 #include "../../include/golhip.h"
 #include "gol_kernels.h"
+#include "gol_rule.h"
 
 // Internal linkage across units: nothing in namespace gh is a dynamic symbol.
 #define GOLHIP_HIDDEN __attribute__((visibility("hidden")))
@@ -90,6 +92,7 @@ struct Counters {
     int64_t flip_resident = 0;  // K5r launches (flip_overlap 2)
     int64_t view_frames = 0;    // frames rendered (K7)
     int64_t pad_launches = 0;   // seam refreshes of the padded torus, one per wide launch
+    int64_t rule_launches = 0;  // of step_launches, those on K11
 };
 // ... and the GOLHIP_FLAG_TIMING sums of the timed spans, by kind (drain_events)
 struct Millis {
@@ -145,6 +148,12 @@ struct golhip {
     int cu_count = 0;           // CUs the launches are planned for (option "cu_count": fewer)
     int dev_cu = 0;             // the device's CUs
     int fill_skip = 1;          // option "fill_skip"
+    // the Life-like rule (golhip_set_rule): two 9-bit masks, Conway's by default.  A handle with another
+    // rule (or, tests, option "rule_kernel") steps on K11 (gol_rule.hip): canonical words, per-launch only
+    uint32_t birth = 0x008, survive = 0x00C;
+    int rule_kernel = 0;            // option "rule_kernel" (test hook): 1 a Conway handle on K11 too, 2 K11's dynamic policy always
+    bool conway() const { return birth == 0x008 && survive == 0x00C; }
+    bool rule_path() const { return !conway() || rule_kernel != 0; }
     int last_variant = 1;           // kernel family of the last step launch (golhip_perf kernel_variant)
     int skew = 1;                   // option "skew": skewed band stacks (K1w) for per-launch steps
     int skew_young = 0;             // option "skew_young": band height of waves 4..7, % of waves 0..3's (0: by kernel)

@@ -37,7 +37,9 @@ namespace {
 // kPathSwitch: a tuning knob that only picks between two code paths of one
 // plan (same launches, same results); it needs the tuning consent too, but
 // golhip_build_info()'s CONSENT_TUNING names the knobs of the plans alone.
-enum Consent : unsigned { kProduct = 1, kTuning = 2, kMeasurement = 4, kTestHook = 8, kPathSwitch = 16 };
+// kUnlisted: golhip_build_info()'s lists do not name the option (a hook that
+// gives the same boards through another kernel, like kPathSwitch's knobs).
+enum Consent : unsigned { kProduct = 1, kTuning = 2, kMeasurement = 4, kTestHook = 8, kPathSwitch = 16, kUnlisted = 32 };
 
 constexpr int64_t kAny = INT64_MAX;  // lo = -kAny, hi = kAny: every value
 
@@ -141,6 +143,9 @@ constexpr Option kOptions[] = {
     // test hook: several resident launches in one step
     {"resident_max_turns", kTestHook, RANGE(1, golk::kResidentMaxTurns), &golhip::resident_max, false, false, nullptr},
     {"flip_debug", kMeasurement | kTestHook, RANGE(0, 7), nullptr, false, false, set_flip_debug},  // (by bit: the handler)
+    // test hook: 1 a Conway handle steps on K11 too (its static policy), 2 K11's dynamic policy for
+    // every rule, the listed ones included; the reference's golden boards then judge both policies
+    {"rule_kernel", kTestHook | kUnlisted, RANGE(0, 2), &golhip::rule_kernel, false, true, nullptr},
 };
 #undef RANGE
 #undef BOOLEAN
@@ -172,7 +177,7 @@ int refuse(const Option &o, int64_t value) {
 std::string consent_list(unsigned cls) {
     std::string s;
     for (const Option &o : kOptions) {
-        if (!(o.consent & cls)) continue;
+        if (!(o.consent & cls) || (o.consent & kUnlisted)) continue;
         if (!s.empty()) s += ",";
         s += o.key;
         if (o.handler == set_flip_debug) s += cls == kMeasurement ? ":1-3" : ":4";

@@ -20,6 +20,9 @@ bool pad_applies(golhip_t h) {
 // or more won at every size measured (100^2: 2.2x at 2 turns; 16385^2: 31x),
 // one-turn calls from 1000^2 on (1.3x; 16385^2: 25x) but lost at 100^2 (0.96x,
 // every repetition), so below the smallest board they won at they stay on K1g.
+// Measured on Conway's kernels; a handle with another rule (K11 on the wide
+// board, K11's one-turn any-width form instead of K1g) keeps it until its own
+// sweep exists.
 struct PadRule {
     int64_t min_cells, min_turns;
 };
@@ -93,8 +96,13 @@ static void take_settings(golhip_t h, golhip *w) {
     w->stream = h->stream;
     w->flags = h->flags;
     if (w->wpl_opt != h->wpl_opt || w->cu_count != h->cu_count || w->fill_skip != h->fill_skip ||
-        w->paired_bands != h->paired_bands)
+        w->paired_bands != h->paired_bands || w->birth != h->birth || w->survive != h->survive ||
+        w->rule_kernel != h->rule_kernel)
         for (int &c : w->auto_rpw) c = 0;
+    // the owner's rule: ghost columns are copies of real ones under any radius-1 rule, B0 included
+    w->birth = h->birth;
+    w->survive = h->survive;
+    w->rule_kernel = h->rule_kernel;
     w->wpl_opt = h->wpl_opt;
     w->cu_count = h->cu_count;
     w->fill_skip = h->fill_skip;
@@ -156,6 +164,7 @@ int pad_step(golhip_t h, int64_t nturns, bool *ran) {
     h->n.skew_half_launches += w->n.skew_half_launches;
     h->n.pair_launches += w->n.pair_launches;
     h->n.pair_turns += w->n.pair_turns;
+    h->n.rule_launches += w->n.rule_launches;
     h->last_variant = w->last_variant;
     *ran = true;
     return GOLHIP_OK;
@@ -281,6 +290,7 @@ int pad_group_step(golhip_t *hs, int32_t n, int64_t nturns, hipEvent_t *ready, b
         h->n.skew_half_launches += w->n.skew_half_launches;
         h->n.pair_launches += w->n.pair_launches;
         h->n.pair_turns += w->n.pair_turns;
+        h->n.rule_launches += w->n.rule_launches;
         h->n.halo_bytes += w->n.halo_bytes;
         h->n.halo_exchanges += w->n.halo_exchanges;
         h->last_variant = w->last_variant;

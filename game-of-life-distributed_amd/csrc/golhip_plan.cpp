@@ -104,6 +104,7 @@ static constexpr int64_t kPersistAutoMaxBytes = 64ll << 20;
 static int wpl_per_launch(golhip_t h);
 static bool skew_fills(golhip_t h);
 bool persist_on(golhip_t h) {
+    if (h->rule_path()) return false;  // K11 has no resident form
     // a multi-rank ring never runs the resident kernel (try_persist_halo):
     // plan words per lane and halos for the per-launch kernels that do run
     if (h->ringed() && h->nranks > 1) return false;
@@ -119,7 +120,7 @@ bool persist_on(golhip_t h) {
 // shift work per word but quantises tiles at 124 words and halves the band
 // height; the option, or whichever plan_rate prefers.
 int wpl_for(golhip_t h) {
-    if (h->W % 64 != 0) return 1;
+    if (h->W % 64 != 0 || h->rule_path()) return 1;  // (K11: canonical words, one a lane)
     if (h->wpl_opt == 1 || h->wpl_opt == 2) return h->wpl_opt;
     if (h->wpl_opt == 4) return h->W % 128 == 0 ? 4 : 2;
     if ((!h->torus() && !h->ringed()) || !persist_on(h)) return wpl_per_launch(h);
@@ -169,6 +170,13 @@ int want_il(golhip_t h) { return wpl_for(h) >= 2 ? wpl_for(h) : 0; }
 // all come from one neighbour strip, so depth <= strip rows.
 int depth_cap(golhip_t h, bool halo) {
     if (h->W % 32 != 0) return 1;  // generic kernel: one turn per launch
+    if (h->rule_path()) {
+        // K11's depths (gol_rule.h): every depth depth_plan returns under 16; a
+        // cap of exactly 9 would name the quads' own depth
+        int cap = std::min(h->tb_depth, golk::kRuleMaxDepth);
+        if (halo) cap = std::min(cap, sched_rows(h));
+        return cap == 9 ? 8 : cap;
+    }
     // a strip between exchanges runs the resident kernel (its depths) when on
     const int wpl = wpl_for(h);
     int cap = std::min(h->tb_depth, (halo && persist_on(h)) ? golk::persist_max_depth(wpl) : golk::max_depth_for(wpl));
@@ -224,6 +232,11 @@ bool tb_paired(golhip_t h) { return h->paired_bands && h->fill_skip; }
 int rows_per_wave_for(golhip_t h, int depth) {
     if (h->rows_per_wave > 0) return h->rows_per_wave;
     int &c = h->auto_rpw[depth_index(depth)];
+    if (c == 0 && h->rule_path()) {
+        const int slots =
+            h->cu_count * golk::rule_wave_slots_per_cu(depth, h->W, h->birth, h->survive, h->rule_kernel == 2);
+        c = golk::auto_rows_per_wave(h->Ww, h->rows, depth, std::max(slots, 1), false, 1, false);
+    }
     if (c == 0) {
         const int wpl = wpl_for(h);
         const int slots = h->cu_count * golk::tb_wave_slots_per_cu(depth, wpl, tb_paired(h));

@@ -139,6 +139,18 @@ int golhip_pattern_read(const char *path, uint32_t *words, uint64_t cap_words, g
     return GOLHIP_OK;
 }
 
+int golhip_pattern_rule(const char *path, uint32_t *birth, uint32_t *survive) {
+    if (!path || !birth || !survive) return fail(GOLHIP_EINVAL, "null argument");
+    golpat::Info pi;
+    golpat::RuleMode mode;  // kReport
+    std::string why;
+    if (golpat::read(path, nullptr, 0, &pi, &why, [](const golpat::Info &, std::string *) { return true; }, &mode))
+        return fail(GOLHIP_EINVAL, "%s", why.c_str());
+    *birth = mode.found_birth;
+    *survive = mode.found_survive;
+    return GOLHIP_OK;
+}
+
 int golhip_stamp_file(golhip_t *hs, int32_t n, const char *path, int32_t x0, int32_t y0, int32_t op,
                       golhip_pattern_info_t *info) {
     if (!path) return fail(GOLHIP_EINVAL, "path is null");
@@ -153,9 +165,15 @@ int golhip_stamp_file(golhip_t *hs, int32_t n, const char *path, int32_t x0, int
     };
     golpat::Info pi;
     std::string why;
-    if (golpat::read(path, nullptr, 0, &pi, &why, fits)) return fail(GOLHIP_EINVAL, "%s", why.c_str());
+    // a Conway board takes what it always took; a board with another rule takes a file of that rule, or of none
+    golpat::RuleMode mode;
+    mode.kind = golpat::RuleMode::kAccept;
+    mode.birth = hs[0]->birth;
+    mode.survive = hs[0]->survive;
+    golpat::RuleMode *rm = hs[0]->conway() ? nullptr : &mode;
+    if (golpat::read(path, nullptr, 0, &pi, &why, fits, rm)) return fail(GOLHIP_EINVAL, "%s", why.c_str());
     std::vector<uint32_t> words((size_t)pi.words());
-    if (golpat::read(path, words.data(), words.size(), &pi, &why, fits)) return fail(GOLHIP_EINVAL, "%s", why.c_str());
+    if (golpat::read(path, words.data(), words.size(), &pi, &why, fits, rm)) return fail(GOLHIP_EINVAL, "%s", why.c_str());
     if (int rc = golhip_group_stamp_bits(hs, n, words.data(), (int32_t)pi.width, (int32_t)pi.height, x0, y0, op)) return rc;
     if (info) fill_info(pi, info);
     return GOLHIP_OK;

@@ -100,10 +100,15 @@ static int launch_rows(golhip_t h, int depth, unsigned long long *alive, bool ha
     golk::StepArgs a = step_args(h, alive, halo);
     if (lo != 0 || hi != h->rows) shift_rows(a, lo, hi);
     const int wpl = wpl_for(h);
+    const bool rule = h->rule_path();  // K11: canonical words, one word per lane, plain bands
+    const bool dyn = h->rule_kernel == 2;
     if (a.rows_out == h->rows) {
         a.rows_per_wave = rows_per_wave_for(h, depth);
     } else if (h->rows_per_wave > 0) {
         a.rows_per_wave = h->rows_per_wave;
+    } else if (rule) {
+        const int slots = h->cu_count * golk::rule_wave_slots_per_cu(depth, h->W, h->birth, h->survive, dyn);
+        a.rows_per_wave = golk::auto_rows_per_wave(h->Ww, a.rows_out, depth, std::max(slots, 1), false, 1, false);
     } else {
         const int slots = h->cu_count * golk::tb_wave_slots_per_cu(depth, wpl, tb_paired(h));
         a.rows_per_wave = golk::auto_rows_per_wave(h->Ww, a.rows_out, depth, std::max(slots, 1), h->fill_skip, wpl,
@@ -111,11 +116,14 @@ static int launch_rows(golhip_t h, int depth, unsigned long long *alive, bool ha
     }
     // a wave's buffer-store range (two bands of a paired region) must stay < 2 GiB
     a.rows_per_wave = (int)std::min<int64_t>(a.rows_per_wave, ((1ll << 31) - 1) / (8ll * h->Ww));
+    if (rule && h->il != 0) return fail(GOLHIP_EINVAL, "the rule kernel steps canonical words (layout %d)", h->il);
     if (int rc = span_begin(h, st)) return rc;
     hipError_t e;
     golk::SkewArgs sk{};
-    const bool skew = skew_plan(h, depth, wpl, a, &sk);
-    if (skew) {
+    const bool skew = !rule && skew_plan(h, depth, wpl, a, &sk);
+    if (rule) {
+        e = golk::launch_step_rule(a, depth, h->birth, h->survive, st, dyn);
+    } else if (skew) {
         sk.base = a;
         e = golk::launch_skew(sk, depth, wpl, st);
     } else if (h->W % 32 == 0) {
@@ -123,10 +131,11 @@ static int launch_rows(golhip_t h, int depth, unsigned long long *alive, bool ha
     } else {
         e = golk::launch_step_generic(a, st);
     }
-    h->last_variant = h->W % 32 != 0 ? 0 : skew ? 3 : 1;
+    h->last_variant = rule ? 5 : h->W % 32 != 0 ? 0 : skew ? 3 : 1;
     if (e != hipSuccess) return fail(GOLHIP_EHIP, "step launch: %s", hipGetErrorString(e));
     if (int rc = span_end(h, 0, true)) return rc;
     h->n.step_launches++;
+    h->n.rule_launches += rule;
     h->n.skew_launches += skew;
     h->n.skew_half_launches += skew && sk.half;
     if (skew && sk.pairs) {
@@ -510,6 +519,8 @@ int group_check(golhip_t *hs, int32_t n, bool need_board) {
         if (need_board && !hs[i]->loaded) return fail(GOLHIP_EINVAL, "strip %d has no board", i);
         if (hs[i]->W != hs[0]->W || hs[i]->H != hs[0]->H || hs[i]->nranks != 1)
             return fail(GOLHIP_EINVAL, "strip %d does not belong to the group", i);
+        if (hs[i]->birth != hs[0]->birth || hs[i]->survive != hs[0]->survive)
+            return fail(GOLHIP_EINVAL, "strip %d has another rule than strip 0", i);
         const int expect_row0 = i == 0 ? 0 : hs[i - 1]->row0 + hs[i - 1]->rows;
         if (hs[i]->row0 != expect_row0) return fail(GOLHIP_EINVAL, "strip %d starts at %d, expected %d", i, hs[i]->row0, expect_row0);
     }
@@ -683,6 +694,7 @@ int golhip_comm_init(golhip_t h, const uint8_t id[GOLHIP_UNIQUE_ID_BYTES], int32
     std::lock_guard<std::mutex> g(h->mu);
     if (int rc = set_dev(h)) return rc;
     if (h->ringed()) return fail(GOLHIP_EINVAL, "comm already initialised");
+    if (!h->conway()) return fail(GOLHIP_EINVAL, "a ring runs Conway's B3/S23 only: this handle has another rule (golhip_set_rule)");
     if (nranks > 1 && h->rows < 1) return fail(GOLHIP_EINVAL, "empty strip");
     ncclUniqueId u;
     memcpy(&u, id, sizeof u);
@@ -711,6 +723,7 @@ int golhip_test_ring_init(golhip_t h, int32_t nranks, int32_t rank, int32_t ring
     if (!fn || nranks < 1 || rank < 0 || rank >= nranks) return fail(GOLHIP_EINVAL, "rank %d of %d", rank, nranks);
     std::lock_guard<std::mutex> g(h->mu);
     if (h->ringed()) return fail(GOLHIP_EINVAL, "comm already initialised");
+    if (!h->conway()) return fail(GOLHIP_EINVAL, "a ring runs Conway's B3/S23 only: this handle has another rule (golhip_set_rule)");
     if (!h->strip || h->rows < 1 || ring_rows < 1 || ring_rows > h->rows)
         return fail(GOLHIP_EINVAL, "a strip handle and 1 <= ring_rows <= its rows");
     h->xport = fn;

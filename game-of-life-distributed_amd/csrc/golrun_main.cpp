@@ -35,6 +35,9 @@
 // (x, y), in the order given, before the first event (gol_host.h
 // RunOptions::blank, patterns).  A bad spec or an unreadable file ends the run
 // with the parser's message, before any event.
+// -rule B36/S23 runs another Life-like rule than Conway's (golhip_rule_parse's
+// spellings; gol_host.h RunOptions::rule); a rule that does not parse ends the
+// run with the parser's message, before any event.
 // The headless drain loop ends at FinalTurnComplete (main.go:59-66) or when
 // the events channel closes.
 #include <sys/stat.h>
@@ -55,7 +58,7 @@ namespace {
     std::fprintf(stderr, "golrun: %s\nusage: golrun [-t threads] [-w width] [-h height] [-turns n] [-noVis] "
                          "[-root dir] [-device n] [-viewScale n] [-viewEvery n] [-viewDir dir] [-viewStrips] "
                          "[-checkpoint path] [-checkpointEvery n] [-resume path] [-streamImages] [-imageEvery n] [-blank] "
-                         "[-pattern path@x,y[,op]]...\n", msg);
+                         "[-pattern path@x,y[,op]]... [-rule B36/S23]\n", msg);
     std::exit(2);
 }
 
@@ -126,6 +129,12 @@ int main(int argc, char **argv) {
             opt.image_every = parse_int(value(), "imageEvery");
         } else if (key == "-blank") {
             opt.blank = eq == std::string::npos || val == "true" || val == "1";
+        } else if (key == "-rule") {
+            const std::string text = value();
+            if (golhip_rule_parse(text.c_str(), &opt.rule.birth, &opt.rule.survive) != GOLHIP_OK) {
+                std::fprintf(stderr, "golrun: %s\n", golhip_last_error());
+                return 1;
+            }
         } else if (key == "-pattern") {
             try {
                 opt.patterns.push_back(gol::ParsePattern(value()));

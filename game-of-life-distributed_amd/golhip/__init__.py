@@ -63,7 +63,7 @@ class Perf(ctypes.Structure):
         ("skew_launches", ctypes.c_int64),
         ("halo_exchanges", ctypes.c_int64),
         ("halo_ms", ctypes.c_double),
-        ("reserved2", ctypes.c_int64),
+        ("rule_launches", ctypes.c_int64),
         ("skew_half_launches", ctypes.c_int64),
         ("lds_launches", ctypes.c_int64),
         ("pair_launches", ctypes.c_int64),
@@ -178,6 +178,11 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "golhip_set_option": ([H, ctypes.c_char_p, i64], ctypes.c_int),
         "golhip_set_pad_step": ([H, i32], ctypes.c_int),
         "golhip_group_set_pad_step": ([P(H), i32, i32], ctypes.c_int),
+        "golhip_rule_parse": ([ctypes.c_char_p, P(u32), P(u32)], ctypes.c_int),
+        "golhip_rule_format": ([u32, u32, ctypes.c_char_p, u64], ctypes.c_int),
+        "golhip_set_rule": ([H, u32, u32], ctypes.c_int),
+        "golhip_rule": ([H, P(u32), P(u32)], ctypes.c_int),
+        "golhip_pattern_rule": ([ctypes.c_char_p, P(u32), P(u32)], ctypes.c_int),
         "golhip_comm_unique_id": ([ctypes.c_char_p], ctypes.c_int),
         "golhip_comm_init": ([H, ctypes.c_char_p, i32, i32], ctypes.c_int),
         "golhip_comm_info": ([H, P(i32), P(i32), P(i32)], ctypes.c_int),
@@ -247,6 +252,28 @@ def device_count() -> int:
     n = ctypes.c_int32(0)
     _check(load().golhip_device_count(ctypes.byref(n)))
     return n.value
+
+
+CONWAY = (0x008, 0x00C)  # (birth, survive) masks of B3/S23
+
+
+def rule_parse(text: str) -> tuple[int, int]:
+    """golhip_rule_parse: "B36/S23" (either case, either half empty) or the
+    legacy "23/36" -> (birth, survive), bit n of each for n alive neighbours."""
+    b, s = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    _check(load().golhip_rule_parse(text.encode(), ctypes.byref(b), ctypes.byref(s)))
+    return b.value, s.value
+
+
+def rule_format(birth: int, survive: int) -> str:
+    """golhip_rule_format: the canonical spelling, digits ascending ("B36/S23")."""
+    buf = ctypes.create_string_buffer(32)
+    _check(load().golhip_rule_format(birth, survive, buf, len(buf)))
+    return buf.value.decode()
+
+
+def _rule_masks(rule) -> tuple[int, int]:
+    return rule_parse(rule) if isinstance(rule, str) else (int(rule[0]), int(rule[1]))
 
 
 def halo_plan(width: int, strip_rows: int, nranks: int, rank: int, depth: int) -> dict:
@@ -361,6 +388,18 @@ class Board:
         """golhip_set_pad_step: widths that are no multiple of 32 on the fast
         kernels as a padded torus: -1 the measured rule (default), 0 never, 1 always."""
         _check(load().golhip_set_pad_step(self._h, mode))
+
+    def set_rule(self, rule) -> None:
+        """golhip_set_rule: the Life-like rule of the turns enqueued from now
+        on, as "B36/S23" or (birth, survive) masks."""
+        b, s = _rule_masks(rule)
+        _check(load().golhip_set_rule(self._h, b, s))
+
+    def rule(self) -> tuple[int, int]:
+        """golhip_rule: this board's (birth, survive) masks."""
+        b, s = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        _check(load().golhip_rule(self._h, ctypes.byref(b), ctypes.byref(s)))
+        return b.value, s.value
 
     def set_stream(self, stream_ptr: int) -> None:
         _check(load().golhip_set_stream(self._h, ctypes.c_void_p(stream_ptr)))
@@ -613,6 +652,12 @@ def group_set_pad_step(boards: list[Board], mode: int) -> None:
     (default), 0 never, 1 always."""
     arr = (ctypes.c_void_p * len(boards))(*[b.handle for b in boards])
     _check(load().golhip_group_set_pad_step(arr, len(boards), mode))
+
+
+def group_set_rule(boards: list[Board], rule) -> None:
+    """Board.set_rule on every strip of a group (a group's calls need one rule on all)."""
+    for b in boards:
+        b.set_rule(rule)
 
 
 def group_flip_stream(boards: list[Board], nturns: int, cap: int, fmt: int = FLIPS_XY, out: np.ndarray | None = None):
@@ -1118,6 +1163,14 @@ def pattern_info(path: str) -> dict:
     return info.as_dict()
 
 
+def pattern_rule(path: str) -> tuple[int, int]:
+    """golhip_pattern_rule: the (birth, survive) masks an RLE file's header
+    names; Conway's where it names none or the file is a PGM (no device)."""
+    b, s = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    _check(load().golhip_pattern_rule(os.fsencode(path), ctypes.byref(b), ctypes.byref(s)))
+    return b.value, s.value
+
+
 def pattern_read(path: str) -> np.ndarray:
     """golhip_pattern_read: the pattern file's cells as a (height, width) bool array (no device)."""
     info = PatternInfo()
@@ -1142,6 +1195,20 @@ def stamp_file(boards, path: str, x0: int, y0: int, op: int = STAMP_OR) -> dict:
 
 
 # Numpy restatements for the tests; they share no code with the C++.
+def life_like_np(cells: np.ndarray, birth: int, survive: int, turns: int = 1) -> np.ndarray:
+    """`turns` turns of the Life-like rule (birth, survive) on a torus of 0/255
+    bytes: bit n of `birth` brings a dead cell with n alive neighbours (of 8)
+    to life, bit n of `survive` keeps an alive one."""
+    a = (np.asarray(cells) == 255).astype(np.uint8)
+    bt = np.array([(birth >> n) & 1 for n in range(9)], dtype=np.uint8)
+    st = np.array([(survive >> n) & 1 for n in range(9)], dtype=np.uint8)
+    for _ in range(turns):
+        rows = a + np.roll(a, 1, axis=0) + np.roll(a, -1, axis=0)
+        n = rows + np.roll(rows, 1, axis=1) + np.roll(rows, -1, axis=1) - a
+        a = np.where(a == 1, st[n], bt[n]).astype(np.uint8)
+    return a * np.uint8(255)
+
+
 def rle_parse_np(text: str) -> np.ndarray:
     """The cells of RLE text as a (y, x) bool array.  Raises ValueError where
     the library refuses the file."""
@@ -1304,7 +1371,7 @@ class Run:
                  keys: bool = False, quirks: bool = False, cell_events: bool = True, turn_events: bool = True,
                  events_cap: int = 0, ticker_ms: int = 0, view: dict | None = None, checkpoint: dict | None = None,
                  resume: str | None = None, stream_images: bool = False, image_every: int = 0, blank: bool = False,
-                 patterns=None):
+                 patterns=None, rule=None):
         """view: the live view (golrun_start_view), dict(scale=..., every=1,
         x0=0, y0=0, out_w=None, out_h=None, fmt=VIEW_ARGB, strips=False);
         missing out_w / out_h are the largest that fit.  Run.view_frame()
@@ -1320,12 +1387,21 @@ class Run:
         images/<W>x<H>.pgm.  patterns: [(path, x, y[, op]), ...], pattern
         files (RLE or PGM) stamped in order, top-left corner at the torus cell
         (x, y), after the initial board is there and before any event; op is
-        "copy", "or" (the default), "xor" or "clear" (or a STAMP_* number)."""
+        "copy", "or" (the default), "xor" or "clear" (or a STAMP_* number).
+        rule: the run's Life-like rule, "B36/S23" or (birth, survive) masks
+        (None: Conway's); a resumed run names it again, pattern files must
+        name it or none."""
         lib = load_host()
+        rule_word = 0
+        if rule is not None:
+            rb, rs = _rule_masks(rule)
+            if not (0 <= rb <= 0x1FF and 0 <= rs <= 0x1FF):
+                raise ValueError("rule masks above 0x1FF")
+            rule_word = 0 if (rb, rs) == CONWAY else 0x40000 | rs << 9 | rb
         flags = (FLAG_KEYS if keys else 0) | (FLAG_REF_QUIRKS if quirks else 0) | \
             (0 if cell_events else FLAG_NO_CELL_EVENTS) | (0 if turn_events else FLAG_NO_TURN_EVENTS)
         more = checkpoint is not None or resume is not None or stream_images or image_every != 0 or blank or \
-            bool(patterns)  # golrun_start_opts
+            bool(patterns) or rule_word != 0  # golrun_start_opts
         spec = None
         if patterns:
             ops = {STAMP_COPY: "copy", STAMP_OR: "or", STAMP_XOR: "xor", STAMP_CLEAR: "clear"}
@@ -1355,6 +1431,7 @@ class Run:
             ro.reserved[1] = 1 if stream_images else 0
             ro.reserved[2] = ctypes.addressof(spec) if spec is not None else 0  # (copied before the call returns)
             ro.reserved[3] = 1 if blank else 0
+            ro.reserved0 = rule_word
         if view is not None:
             unknown = set(view) - {"scale", "every", "x0", "y0", "out_w", "out_h", "fmt", "strips"}
             if unknown or "scale" not in view:

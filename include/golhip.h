@@ -83,8 +83,10 @@ typedef struct golhip_perf {
     int32_t tb_depth;         /* most turns one step launch fuses (the setting,
                                  capped by the kernel's words per lane)       */
     int32_t rows_per_wave;    /* rows streamed per wavefront (full-depth launch)*/
-    int32_t kernel_variant;   /* 0 = generic (width % 32 != 0), 1 = bit-sliced
-                                 (after a padded step: the wide board's)     */
+    int32_t kernel_variant;   /* 0 = generic (width % 32 != 0), 1 = bit-sliced, 3 = skewed
+                                 band stacks, 4 = resident LDS bands, 5 = the rule kernel
+                                 (K11, golhip_set_rule; any width); after a padded step:
+                                 the wide board's                             */
     int32_t words_per_lane;   /* 1, 2 (interleaved pairs) or 4 (quads); 0 generic */
     int64_t persist_fallbacks; /* resident launches that timed out (not all workgroups
                                   co-resident) and were re-run on per-launch kernels */
@@ -104,7 +106,9 @@ typedef struct golhip_perf {
     int64_t halo_exchanges;   /* halo exchanges posted (RCCL ring)               */
     double halo_ms;           /* their summed time on the stream they ran on
                                  (GOLHIP_FLAG_TIMING)                           */
-    int64_t reserved2;        /* 0 (was overlap_launches: option "overlap" retired in round 5) */
+    int64_t rule_launches;    /* of step_launches, those on the rule kernel (K11,
+                                 kernel_variant 5; the offset of the retired
+                                 overlap_launches / reserved2)                   */
     int64_t skew_half_launches; /* of skew_launches, those on half-wave tiles    */
     int64_t lds_launches;     /* of persist_launches, those that ran resident LDS
                                  bands (gol_lds_band_kernel, kernel_variant 4)  */
@@ -216,7 +220,11 @@ int golhip_set_rows_per_wave(golhip_t h, int32_t rows);
  * workgroup 0 never reports in any launch, 2: only in a step's first
  * resident launch; the neighbours' bounded waits time out and the step is
  * restored and re-run), "resident_max_turns" (lowers the turns one resident
- * launch takes, so a step runs several), "flip_debug" 4.
+ * launch takes, so a step runs several), "flip_debug" 4, "rule_kernel" (1: a
+ * handle with Conway's rule steps on the rule kernel K11 too, on its static
+ * policy; 2: K11's dynamic policy for every rule, those with a static instance
+ * included; same boards either way, so the golden boards judge both policies;
+ * not listed by golhip_build_info()).
  *
  * golhip_build_info() lists the three consent sets and the product options.
  * Retired (refused as unknown keys): "split", "lds_split", "skew_nst",
@@ -240,6 +248,38 @@ int golhip_set_option(golhip_t h, const char *key, int64_t value);
  * strips of a group have golhip_group_set_pad_step, and a ring's steps keep
  * the any-width kernel.  perf: pad_launches. */
 int golhip_set_pad_step(golhip_t h, int32_t mode);
+
+/* ---- Life-like rules -------------------------------------------------- */
+/* A rule is two 9-bit masks: bit n of `birth`, a dead cell with n alive
+ * neighbours (of 8, the centre excluded) comes alive; bit n of `survive`, an
+ * alive cell with n stays alive.  Conway's B3/S23 is birth 0x008, survive
+ * 0x00C, the rule of every new handle.  B0 is legal (well defined on a torus).
+ *
+ * golhip_rule_parse reads "B<digits>/S<digits>" in either letter case, either
+ * half possibly empty ("B2/S"), or the legacy "<survive digits>/<birth digits>"
+ * ("23/3"); white space around it, digits 0..8 in any order, none repeated.
+ * Anything else (a digit 9, no '/', Generations "/C", non-totalistic
+ * suffixes) is GOLHIP_EINVAL with a message naming the fault.
+ * golhip_rule_format writes the canonical "B36/S23" (digits ascending, NUL
+ * terminated); GOLHIP_ERANGE if `cap` bytes do not hold it, GOLHIP_EINVAL for a
+ * mask above 0x1FF. */
+int golhip_rule_parse(const char *text, uint32_t *birth, uint32_t *survive);
+int golhip_rule_format(uint32_t birth, uint32_t survive, char *out, uint64_t cap);
+/* The rule of the turns enqueued from now on (masks above 0x1FF: GOLHIP_EINVAL).
+ * Any time on a handle without a communicator; the board, the turn, the kept
+ * count and the flip list stay.  A handle with another rule than Conway's steps
+ * on the rule kernel (K11, canonical words, up to 16 turns a launch; widths
+ * that are no multiple of 32 through the padded torus or one turn a launch),
+ * never on the resident or skewed kernels, and its flip streams take one turn
+ * and one three-pass compaction a turn (same contract).  Every other call
+ * works on it unchanged.  The strips of one group must all have the same rule
+ * (every call that takes a group: GOLHIP_EINVAL otherwise).
+ * Rings: a handle with a communicator (golhip_comm_init, one-rank rings and
+ * golhip_test_ring_init's included) refuses every rule but Conway's, and
+ * golhip_comm_init / golhip_test_ring_init refuse a handle that has another:
+ * the ranks of a ring could disagree on the rule and nobody would notice. */
+int golhip_set_rule(golhip_t h, uint32_t birth, uint32_t survive);
+int golhip_rule(golhip_t h, uint32_t *birth, uint32_t *survive);
 
 /* ---- multi-GPU -------------------------------------------------------- */
 /* RCCL ring of strips: rank r's neighbours are r-1 (rows above) and r+1
@@ -513,7 +553,11 @@ int golhip_group_view_stream(golhip_t *hs, int32_t n, int64_t nturns, int64_t ev
  * is not for handles of an RCCL ring (GOLHIP_EINVAL, one-rank rings included).
  * golhip_checkpoint_load takes the handle of a one-rank ring as the whole torus
  * it is (the turns after it are planned as before the load) and
- * refuses a rank of a larger ring: it is no group (GOLHIP_EINVAL). */
+ * refuses a rank of a larger ring: it is no group (GOLHIP_EINVAL).
+ *
+ * The file does not record the rule (golhip_set_rule; format version 1
+ * stays): golhip_checkpoint_load leaves the handles' rule as it is, and a
+ * process that resumes a run on another rule than Conway's sets it again. */
 typedef struct golhip_ckpt golhip_ckpt;
 typedef struct golhip_ckpt_opts {
     int32_t chunk_rows;   /* rows a staging buffer holds; 0 = automatic (16 MiB)  */
@@ -699,9 +743,19 @@ int golhip_pattern_info(const char *path, golhip_pattern_info_t *info);
  * info->width and height set (alive 0): the size is checked before anything is
  * written.  Needs no device. */
 int golhip_pattern_read(const char *path, uint32_t *words, uint64_t cap_words, golhip_pattern_info_t *info);
+/* The rule an RLE file's header names, as golhip_rule_parse's masks; Conway's
+ * where it names none or the file is a PGM.  GOLHIP_EINVAL for a rule
+ * golhip_rule_parse refuses and for the file errors of golhip_pattern_info
+ * (which, like golhip_pattern_read, goes on refusing every rule but
+ * Conway's).  Needs no device. */
+int golhip_pattern_rule(const char *path, uint32_t *birth, uint32_t *survive);
 /* golhip_pattern_read and golhip_group_stamp_bits in one call (hs, n: one
  * whole-torus handle or a group of strips).  A pattern larger than the board
- * is refused before its cells are read.  info nullable. */
+ * is refused before its cells are read.  info nullable.
+ * On handles with Conway's rule the file's rule is checked as by
+ * golhip_pattern_info; on handles whose rule is R (golhip_set_rule) an RLE
+ * file must name R (any spelling golhip_rule_parse takes) or no rule at all:
+ * any other is GOLHIP_EINVAL with a message naming both rules. */
 int golhip_stamp_file(golhip_t *hs, int32_t n, const char *path, int32_t x0, int32_t y0, int32_t op,
                       golhip_pattern_info_t *info);
 

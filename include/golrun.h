@@ -107,11 +107,18 @@ int golrun_start_view(int64_t turns, int64_t threads, int64_t width, int64_t hei
  * reserved[3]: blank (RunOptions::blank): 1 starts from an empty board
  * (golhip_clear) instead of images/<W>x<H>.pgm.
  * With resume_path, patterns and blank are refused where the image read
- * fails: a restarted job must not stamp twice. */
+ * fails: a restarted job must not stamp twice.
+ * reserved0: the run's Life-like rule (gol_host.h RunOptions::rule): 0 is
+ * Conway's B3/S23, any other rule is 0x40000 | survive << 9 | birth with the
+ * 9-bit masks of golhip_rule_parse (bit 18 tells B/S with both masks empty
+ * from 0; any other bit set fails the call).  The rule is set on every handle
+ * of the run, strips included, before the initial board's events.  With
+ * resume_path the caller passes the rule again: a checkpoint keeps none.
+ * Pattern files must name the run's rule or none (golhip_stamp_file). */
 typedef struct golrun_opts {
     const golhip_view_t *view;
     int32_t view_every;
-    int32_t reserved0;
+    int32_t reserved0;      /* the rule: 0 Conway, else 0x40000 | survive << 9 | birth */
     const char *checkpoint_path;
     int64_t checkpoint_every;
     const char *resume_path;

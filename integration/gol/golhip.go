@@ -105,6 +105,14 @@ package gol
 //                                golhip_pattern_info_t *info) {
 //     return gh_wrap(golhip_stamp_file(hs, n, path, x0, y0, op, info));
 // }
+// // Life-like rules (golhip_rule_parse, golhip_set_rule): the rule of the turns
+// // enqueued from now on, two 9-bit masks; every strip of a group gets the same.
+// static gh_status gh_rule_parse(const char *text, uint32_t *birth, uint32_t *survive) {
+//     return gh_wrap(golhip_rule_parse(text, birth, survive));
+// }
+// static gh_status gh_set_rule(golhip_t h, uint32_t birth, uint32_t survive) {
+//     return gh_wrap(golhip_set_rule(h, birth, survive));
+// }
 // // The padded torus (int golhip_set_pad_step(golhip_t h, int32_t mode)): a width
 // // that is no multiple of 32 on the fast kernels; -1 the measured rule (the
 // // default, which the engine keeps), 0 never, 1 always.
@@ -143,6 +151,10 @@ type engine struct {
 
 	framesP unsafe.Pointer // golhip_host_alloc buffer of view frames (ARGB8888)
 	frames  []uint32       // a Go view of it
+
+	// Rule is the run's Life-like rule as (birth, survive) masks (golhip.h);
+	// Conway's B3/S23 unless the package variable Rule names another.
+	Rule [2]uint32
 
 	ckpt     *C.golhip_ckpt // the checkpoint in flight (at most one)
 	ckptTurn int            // turn of the last checkpoint begun (-1: none)
@@ -290,9 +302,37 @@ func (e *engine) checkpointWait() {
 	}
 }
 
+// Rule is the Life-like rule of the runs of this process, in any spelling
+// golhip_rule_parse takes ("B36/S23", "23/36"); empty: Conway's B3/S23, or the
+// environment's GOL_RULE.  The reference's Params has no field to carry it.  A
+// run from a checkpoint names it again: the file keeps none.
+var Rule string
+
+// SetRule sets the rule on every handle of the engine (golhip_set_rule); a
+// spelling that does not parse panics with the parser's message.
+func (e *engine) SetRule(text string) {
+	ctext := C.CString(text)
+	defer C.free(unsafe.Pointer(ctext))
+	var b, s C.uint32_t
+	check(C.gh_rule_parse(ctext, &b, &s))
+	for _, h := range e.hs {
+		check(C.gh_set_rule(h, b, s))
+	}
+	e.Rule = [2]uint32{uint32(b), uint32(s)}
+}
+
 // createEngine makes the handles of newEngine / resumeEngine (no board yet).
 func createEngine(p Params) *engine {
-	e := &engine{width: p.ImageWidth, height: p.ImageHeight, ckptTurn: -1}
+	e := &engine{width: p.ImageWidth, height: p.ImageHeight, ckptTurn: -1, Rule: [2]uint32{0x008, 0x00C}}
+	defer func() {
+		rule := Rule
+		if rule == "" {
+			rule = os.Getenv("GOL_RULE")
+		}
+		if rule != "" && len(e.hs) > 0 {
+			e.SetRule(rule)
+		}
+	}()
 	ngpu := envInt("GOL_NGPU", 1)
 	n := envInt("GOL_STRIPS", 0)
 	if n <= 0 {
