@@ -440,6 +440,25 @@ void Run(Params p, Chan<Event> *events, Chan<char32_t> *keyPresses, const RunOpt
         return fname;
     };
 
+    // RunOptions::save_rle: the alive box of the board as out/<W>x<H>x<turn>.rle,
+    // written at a turn boundary (the caller holds `mu`, or no turn is running)
+    // before the image of that turn is begun, so before its ImageOutputComplete.
+    const bool save_rle = opt.save_rle >= 0 ? opt.save_rle != 0 : env_int("GOL_SAVE_RLE", 0) != 0;
+    auto write_rle = [&](int64_t turn) {
+        if (!save_rle) return;
+        const std::string fname = name + "x" + std::to_string(turn) + ".rle";
+        mkdir((opt.root + "/out").c_str(), 0777);
+        const int rc = golhip_save_rle(board.hs.data(), (int32_t)board.hs.size(), (opt.root + "/out/" + fname).c_str(), 0, 0, 0,
+                                       0, 0, nullptr);
+        if (rc == GOLHIP_EINVAL && std::string(golhip_last_error()) == "board is empty") {
+            std::printf("File %s not written: the board is empty\n", fname.c_str());
+        } else {
+            check(rc);
+            std::printf("File %s output done!\n", fname.c_str());
+        }
+        std::fflush(stdout);
+    };
+
     // Streamed: the image is begun at a turn boundary (the caller holds `mu`,
     // or no turn is running) and waited for off it; the file, the line and the
     // event are write_snapshot's.
@@ -572,6 +591,7 @@ void Run(Params p, Chan<Event> *events, Chan<char32_t> *keyPresses, const RunOpt
                 {
                     auto g = lock_mu();  // snapshot at a turn boundary
                     t = turn.load();
+                    write_rle(t);
                     // streamed: only the enqueue holds `mu`; the turn loop steps on while the file is written
                     if (streamed_key) im = image_begin(t);
                     else fname = write_snapshot(t, quirks);
@@ -792,6 +812,7 @@ void Run(Params p, Chan<Event> *events, Chan<char32_t> *keyPresses, const RunOpt
         board.ckpt_wait();  // the last periodic checkpoint is on disk before FinalTurnComplete
         // distributor.go:180-206
         std::vector<util::Cell> alive = board.cells(golhip_alive_cells, false);
+        write_rle(p.Turns);
         if (stream) {
             image_finish(image_begin(p.Turns), p.Turns);  // the run never holds W * H bytes
         } else {
@@ -930,6 +951,7 @@ int golrun_start_opts(int64_t turns, int64_t threads, int64_t width, int64_t hei
     }
     golrun *r = new golrun((size_t)events_cap, (flags & GOLRUN_FLAG_KEYS) != 0);
     if (flags & GOLRUN_FLAG_VIEW_STRIPS) o.view_strips = 1;
+    if (flags & GOLRUN_FLAG_SAVE_RLE) o.save_rle = 1;
     if (view) {
         r->has_view = true;
         o.view = *view;

@@ -455,6 +455,14 @@ struct RunOptions {
     };
     bool blank = false;
     std::vector<Pattern> patterns;
+    // Saved patterns (golhip_save_rle): beside the final image and the images
+    // of `s` and `q`, out/<W>x<H>x<turn>.rle with the alive box of the board at
+    // that turn (one handle or strips), complete before that image's
+    // ImageOutputComplete is sent; never transposed, whatever ref_quirks says.
+    // An empty board writes no file and prints one line saying so.  The
+    // periodic images of image_every get none.  Opt-in: 1 on, 0 off, -1 from
+    // the environment, GOL_SAVE_RLE=1 (unset: off).
+    int save_rle = -1;
     // The Life-like rule of the run (golhip_set_rule; masks as in golhip.h,
     // Conway's by default): set on every handle, strips included, before the
     // initial board's events.  With cell events the batches go through the

@@ -370,6 +370,26 @@ struct StampArgs {
 };
 hipError_t launch_stamp(const StampArgs &a, int il, hipStream_t s);
 
+// gol_extract.hip (K12): the mirror of K10.  ORs columns [sx, sx + sw) of the
+// local rows [row, row + nr) of `rows` (layout il, Ww words a row; read only)
+// into columns [ox, ox + sw) of the nr rows of `out` (canonical words, pww a
+// row, zeroed by the caller; no bit outside the segment is set).  The caller
+// guarantees sx + sw <= W and ox + sw <= 32 pww; the grid is capped.
+struct ExtractArgs {
+    const uint32_t *rows;
+    uint32_t *out;
+    int64_t row, nr;
+    int Ww, pww;
+    int sx, ox, sw;
+};
+hipError_t launch_extract(const ExtractArgs &a, int il, hipStream_t s);
+// gol_extract.hip (K13): ORs the nrows rows `rows` (layout il, Ww words a row,
+// padding bits zero; read only) into the zeroed bitmaps col_or[Ww] (canonical
+// words: bit x, some row has cell x alive) and row_or[ceil(nrows / 32)] (bit r,
+// row r has an alive cell).  The grid is capped.
+hipError_t launch_occupancy(const uint32_t *rows, int64_t nrows, int Ww, int il, uint32_t *col_or, uint32_t *row_or,
+                            hipStream_t s);
+
 // "NAME=value ..." of the build's tuning macros (golhip_build_info).
 const char *build_info();
 

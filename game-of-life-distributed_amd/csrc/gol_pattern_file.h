@@ -14,8 +14,22 @@
 // RuleMode accepts one other rule instead, or reports whichever the file names.
 // A pattern comes out as canonical bit words: ceil(width / 32) uint32 a row,
 // cell (y, x) = bit x % 32 of word x / 32, padding bits zero.
+//
+// RleWriter is the way back (golhip_pattern_write, golhip_save_rle; DESIGN.md
+// §5.22): canonical rows in order, in as many chunks as the caller likes, to
+// "<path>.tmp", renamed over <path> by commit().  It writes Golly's extended
+// header "#CXRLE Pos=x,y Gen=t" (a '#' line to the parser above), the header
+// line with golrule::format's spelling of the rule, and the body in lines of
+// at most 70 characters: counts of 1, trailing dead cells of a row and
+// trailing dead rows left out, '!' at the end.  A pattern with no alive cell
+// is the header and "!".
 #pragma once
+#include <fcntl.h>
+#include <unistd.h>
+
+#include <algorithm>
 #include <cctype>
+#include <cerrno>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -280,5 +294,134 @@ inline int read(const char *path, uint32_t *words, uint64_t cap_words, Info *inf
 inline int read(const char *path, uint32_t *words, uint64_t cap_words, Info *info, std::string *why) {
     return read(path, words, cap_words, info, why, [](const Info &, std::string *) { return true; });
 }
+
+class RleWriter {
+  public:
+    RleWriter() = default;
+    RleWriter(const RleWriter &) = delete;
+    RleWriter &operator=(const RleWriter &) = delete;
+    ~RleWriter() { abandon(); }
+
+    // Opens <path>.tmp and writes the two header lines.  False with *why set; no file is left then.
+    bool open(const char *path, int64_t pw, int64_t ph, uint32_t birth, uint32_t survive, int64_t x0, int64_t y0,
+              int64_t turn, std::string *why) {
+        path_ = path;
+        tmp_ = path_ + ".tmp";
+        pw_ = pw;
+        ph_ = ph;
+        pww_ = (pw + 31) / 32;
+        fd_ = ::open(tmp_.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+        if (fd_ < 0) {
+            *why = "open " + tmp_ + ": " + std::strerror(errno);
+            return false;
+        }
+        out_ = "#CXRLE Pos=" + std::to_string(x0) + "," + std::to_string(y0) + " Gen=" + std::to_string(turn) + "\n";
+        out_ += "x = " + std::to_string(pw) + ", y = " + std::to_string(ph) + ", rule = " + golrule::format(birth, survive) + "\n";
+        return true;
+    }
+
+    // The next nrows rows of the pattern (canonical words, ceil(pw / 32) a row; padding bits are not looked at).
+    bool feed(const uint32_t *words, int64_t nrows, std::string *why) {
+        for (int64_t r = 0; r < nrows; ++r, ++row_) {
+            if (row_ >= ph_) {
+                *why = "RLE: more rows than the header's " + std::to_string(ph_);
+                return fail_(why, nullptr);
+            }
+            const uint32_t *w = words + r * pww_;
+            if (row_ > 0) ++dollars_;  // (a run of empty rows is carried, over chunks too, until a cell follows)
+            int64_t x = 0;             // the end of the row's last alive run
+            for (;;) {
+                const int64_t s = next_(w, x, true);
+                if (s >= pw_) break;
+                const int64_t e = next_(w, s, false);
+                if (dollars_) token_(dollars_, '$');
+                dollars_ = 0;
+                if (s > x) token_(s - x, 'b');
+                token_(e - s, 'o');
+                alive_ += (uint64_t)(e - s);
+                x = e;
+            }
+            if (out_.size() >= (1u << 16) && !flush_(why)) return false;
+        }
+        return true;
+    }
+
+    // '!', fsync, rename over the path.  False with *why set; the .tmp file is gone then.
+    bool commit(std::string *why) {
+        if (fd_ < 0) {
+            *why = "RLE: no file open";
+            return false;
+        }
+        token_(1, '!');
+        out_ += line_ + "\n";
+        line_.clear();
+        if (!flush_(why)) return false;
+        if (::fsync(fd_) != 0) return fail_(why, "fsync ");
+        if (::close(fd_) != 0) {
+            fd_ = -1;
+            ::unlink(tmp_.c_str());
+            *why = "close " + tmp_ + ": " + std::strerror(errno);
+            return false;
+        }
+        fd_ = -1;
+        if (::rename(tmp_.c_str(), path_.c_str()) != 0) {
+            *why = "rename " + tmp_ + ": " + std::strerror(errno);
+            ::unlink(tmp_.c_str());
+            return false;
+        }
+        return true;
+    }
+
+    // Closes and removes the .tmp file of a pattern that is not committed.
+    void abandon() {
+        if (fd_ < 0) return;
+        ::close(fd_);
+        fd_ = -1;
+        ::unlink(tmp_.c_str());
+    }
+
+    uint64_t alive() const { return alive_; }
+
+  private:
+    // The first column >= from of the row whose cell is `alive` (or not); pw_ where there is none.
+    int64_t next_(const uint32_t *w, int64_t from, bool alive) const {
+        for (int64_t q = from >> 5; from < pw_; ++q, from = 32 * q) {
+            uint32_t v = alive ? w[q] : ~w[q];
+            v &= ~0u << (from & 31);
+            if (v) return std::min<int64_t>(32 * q + __builtin_ctz(v), pw_);
+        }
+        return pw_;
+    }
+    void token_(int64_t count, char tag) {
+        std::string t = count == 1 ? std::string() : std::to_string(count);
+        t.push_back(tag);
+        if (line_.size() + t.size() > 70) {
+            out_ += line_ + "\n";
+            line_.clear();
+        }
+        line_ += t;
+    }
+    bool flush_(std::string *why) {
+        size_t done = 0;
+        while (done < out_.size()) {
+            const ssize_t k = ::write(fd_, out_.data() + done, out_.size() - done);
+            if (k < 0 && errno == EINTR) continue;
+            if (k <= 0) return fail_(why, "write ");
+            done += (size_t)k;
+        }
+        out_.clear();
+        return true;
+    }
+    bool fail_(std::string *why, const char *call) {
+        if (call) *why = call + tmp_ + ": " + std::strerror(errno);
+        abandon();
+        return false;
+    }
+
+    std::string path_, tmp_, out_, line_;
+    int fd_ = -1;
+    int64_t pw_ = 0, ph_ = 0, pww_ = 0, row_ = 0, dollars_ = 0;
+    uint64_t alive_ = 0;
+};
 
 }  // namespace golpat

@@ -22,6 +22,7 @@
 //   golhip_ckpt.cpp     checkpoints: shadow copy (K8), drain to a file, verified load
 //   golhip_image.cpp    PGM images: the same shadow copy, expanded to bytes in page-locked memory (K9), streamed load
 //   golhip_stamp.cpp    patterns: an empty board, a rectangle of cells stamped on the torus (K10), pattern files
+//   golhip_extract.cpp  saving patterns: any rectangle read back (K12), the alive box (K13), RLE files
 //   golhip_rule.cpp     Life-like rules: their spelling, golhip_set_rule
 //   golhip_pad.cpp      the padded torus and padded strips: widths that are no multiple of 32 on the fast kernels
 //

@@ -4,7 +4,7 @@
 //   golrun [-t threads] [-w width] [-h height] [-turns n] [-noVis] [-root dir] [-device n]
 //          [-viewScale n] [-viewEvery n] [-viewDir dir] [-viewStrips]
 //          [-checkpoint path] [-checkpointEvery n] [-resume path]
-//          [-streamImages] [-imageEvery n] [-blank] [-pattern path@x,y[,op]]...
+//          [-streamImages] [-imageEvery n] [-blank] [-pattern path@x,y[,op]]... [-saveRle]
 //
 // Same flags, defaults and output as main.go: "Threads: / Width: / Height:"
 // lines, then gol.Run on images/<w>x<h>.pgm with an events channel of
@@ -35,6 +35,9 @@
 // (x, y), in the order given, before the first event (gol_host.h
 // RunOptions::blank, patterns).  A bad spec or an unreadable file ends the run
 // with the parser's message, before any event.
+// -saveRle writes out/<w>x<h>x<turn>.rle, the alive box of the board, beside
+// the final image and the images of s and q (gol_host.h RunOptions::save_rle);
+// an empty board writes none.
 // -rule B36/S23 runs another Life-like rule than Conway's (golhip_rule_parse's
 // spellings; gol_host.h RunOptions::rule); a rule that does not parse ends the
 // run with the parser's message, before any event.
@@ -58,7 +61,7 @@ namespace {
     std::fprintf(stderr, "golrun: %s\nusage: golrun [-t threads] [-w width] [-h height] [-turns n] [-noVis] "
                          "[-root dir] [-device n] [-viewScale n] [-viewEvery n] [-viewDir dir] [-viewStrips] "
                          "[-checkpoint path] [-checkpointEvery n] [-resume path] [-streamImages] [-imageEvery n] [-blank] "
-                         "[-pattern path@x,y[,op]]... [-rule B36/S23]\n", msg);
+                         "[-pattern path@x,y[,op]]... [-rule B36/S23] [-saveRle]\n", msg);
     std::exit(2);
 }
 
@@ -129,6 +132,8 @@ int main(int argc, char **argv) {
             opt.image_every = parse_int(value(), "imageEvery");
         } else if (key == "-blank") {
             opt.blank = eq == std::string::npos || val == "true" || val == "1";
+        } else if (key == "-saveRle") {
+            opt.save_rle = (eq == std::string::npos || val == "true" || val == "1") ? 1 : 0;
         } else if (key == "-rule") {
             const std::string text = value();
             if (golhip_rule_parse(text.c_str(), &opt.rule.birth, &opt.rule.survive) != GOLHIP_OK) {

@@ -230,6 +230,12 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "golhip_pattern_info": ([ctypes.c_char_p, P(PatternInfo)], ctypes.c_int),
         "golhip_pattern_read": ([ctypes.c_char_p, ctypes.c_void_p, u64, P(PatternInfo)], ctypes.c_int),
         "golhip_stamp_file": ([P(H), i32, ctypes.c_char_p, i32, i32, i32, P(PatternInfo)], ctypes.c_int),
+        "golhip_extract_bits": ([H, i32, i32, i32, i32, ctypes.c_void_p, u64], ctypes.c_int),
+        "golhip_group_extract_bits": ([P(H), i32, i32, i32, i32, i32, ctypes.c_void_p, u64], ctypes.c_int),
+        "golhip_alive_box": ([P(H), i32, P(i32), P(i32), P(i32), P(i32)], ctypes.c_int),
+        "golhip_box_interval": ([ctypes.c_void_p, i32, P(i32), P(i32)], ctypes.c_int),
+        "golhip_pattern_write": ([ctypes.c_char_p, ctypes.c_void_p, i32, i32, u32, u32, i32, i32, i64], ctypes.c_int),
+        "golhip_save_rle": ([P(H), i32, ctypes.c_char_p, i32, i32, i32, i32, i32, P(PatternInfo)], ctypes.c_int),
         "golhip_perf": ([H, P(Perf)], ctypes.c_int),
         "golhip_perf_reset": ([H], ctypes.c_int),
         "golhip_persist_trace": ([H, P(u64)], ctypes.c_int),
@@ -564,6 +570,17 @@ class Board:
         out = np.empty((nrows, self.words), dtype=np.uint32)
         _check(load().golhip_snapshot_rows(self._h, row, nrows, _ptr(out)))
         return out
+
+    # saving patterns
+    def extract(self, x0: int, y0: int, w: int, h: int) -> np.ndarray:
+        """golhip_extract_bits: the w x h cells from the torus cell (x0, y0) on,
+        wrapping in x and y, as an (h, w) bool array (a strip: y counts torus
+        rows, rows it does not own are False)."""
+        return _extract(lambda *a: load().golhip_extract_bits(self._h, *a), x0, y0, w, h)
+
+    def alive_box(self) -> tuple[int, int, int, int]:
+        """golhip_alive_box of a whole-torus handle: (x0, y0, w, h), w = h = 0 on an empty board."""
+        return group_alive_box([self])
 
     def board_hash(self) -> int:
         h = ctypes.c_uint64()
@@ -1194,7 +1211,102 @@ def stamp_file(boards, path: str, x0: int, y0: int, op: int = STAMP_OR) -> dict:
     return info.as_dict()
 
 
+# saving patterns
+def _words_to_cells(words: np.ndarray, pw: int) -> np.ndarray:
+    ph, ww = words.shape
+    bits = np.unpackbits(words.astype("<u4").view(np.uint8).reshape(ph, ww * 4), axis=1, bitorder="little")
+    return bits[:, :pw].astype(bool)
+
+
+def _extract(call, x0: int, y0: int, w: int, h: int) -> np.ndarray:
+    ww = (max(w, 0) + 31) // 32
+    words = np.zeros((max(h, 0), ww), dtype=np.uint32)
+    _check(call(x0, y0, w, h, _ptr(words) if words.size else None, words.size))
+    return _words_to_cells(words, w)
+
+
+def group_extract(boards: list[Board], x0: int, y0: int, w: int, h: int) -> np.ndarray:
+    """golhip_group_extract_bits: Board.extract on the board held by a group of strips."""
+    arr, n = _handles(boards)
+    return _extract(lambda *a: load().golhip_group_extract_bits(arr, n, *a), x0, y0, w, h)
+
+
+def group_alive_box(boards) -> tuple[int, int, int, int]:
+    """golhip_alive_box: (x0, y0, w, h) of the smallest box of at most one lap
+    around every alive cell of the torus held by one Board or a group of
+    strips; w = h = 0 on an empty board."""
+    arr, n = _handles(boards)
+    v = [ctypes.c_int32(0) for _ in range(4)]
+    _check(load().golhip_alive_box(arr, n, *[ctypes.byref(x) for x in v]))
+    return tuple(x.value for x in v)
+
+
+def box_interval(bits, n: int | None = None) -> tuple[int, int]:
+    """golhip_box_interval: (start, len) of the shortest cyclic interval over
+    every True of `bits`, a 1-D bool array of the axis' n positions (no device)."""
+    b = np.asarray(bits, dtype=bool).ravel()
+    n = b.size if n is None else n
+    padded = np.zeros(((max(n, 1) + 31) // 32) * 32, dtype=np.uint8)
+    padded[:b.size] = b
+    words = np.packbits(padded, bitorder="little").view("<u4").astype(np.uint32)
+    s, l = ctypes.c_int32(0), ctypes.c_int32(0)
+    _check(load().golhip_box_interval(_ptr(words), n, ctypes.byref(s), ctypes.byref(l)))
+    return s.value, l.value
+
+
+def pattern_write(path: str, cells, rule=None, x0: int = 0, y0: int = 0, turn: int = 0) -> None:
+    """golhip_pattern_write: a 2-D array of cells as an RLE file whose header
+    names `rule` ("B36/S23" or masks; None: Conway's) and whose #CXRLE line
+    carries x0, y0 and turn (no device)."""
+    c = _alive_2d(cells)
+    w = pattern_words_np(c)
+    b, s = CONWAY if rule is None else _rule_masks(rule)
+    _check(load().golhip_pattern_write(os.fsencode(path), _ptr(w), c.shape[1], c.shape[0], b, s, x0, y0, turn))
+
+
+def save_rle(boards, path: str, box=None, chunk_rows: int = 0) -> dict:
+    """golhip_save_rle: the rectangle box = (x0, y0, w, h) of one Board or a
+    group of strips (None: the alive box) as an RLE file, chunk_rows rows at a
+    time; returns pattern_info's dict as the writer counted it."""
+    arr, n = _handles(boards)
+    x0, y0, w, h = (0, 0, 0, 0) if box is None else box
+    info = PatternInfo()
+    _check(load().golhip_save_rle(arr, n, os.fsencode(path), x0, y0, w, h, chunk_rows, ctypes.byref(info)))
+    return info.as_dict()
+
+
 # Numpy restatements for the tests; they share no code with the C++.
+def extract_np(board_cells, x0: int, y0: int, w: int, h: int) -> np.ndarray:
+    """What an extract returns: the w x h cells of the (H, W) board from the
+    torus cell (x0, y0) on, wrapping in x and y, as a bool array."""
+    alive = _alive_2d(np.asarray(board_cells))
+    H, W = alive.shape
+    return alive[np.ix_((y0 + np.arange(h)) % H, (x0 + np.arange(w)) % W)]
+
+
+def _interval_np(occ: np.ndarray) -> tuple[int, int]:
+    """The shortest cyclic interval over every True, the smallest start among
+    equals: a shortest interval starts on a True, so every True is tried as
+    the start and the interval must reach the True farthest ahead of it."""
+    n = occ.size
+    p = np.flatnonzero(occ)
+    if p.size == 0:
+        return 0, 0
+    length = ((p[None, :] - p[:, None]) % n).max(axis=1) + 1
+    k = int(np.argmin(length))  # (the first of equals: p ascends)
+    return int(p[k]), int(length[k])
+
+
+def alive_box_np(board_cells) -> tuple[int, int, int, int]:
+    """What golhip_alive_box returns for the (H, W) board: (x0, y0, w, h)."""
+    alive = _alive_2d(np.asarray(board_cells))
+    if not alive.any():
+        return 0, 0, 0, 0
+    x0, w = _interval_np(alive.any(axis=0))
+    y0, h = _interval_np(alive.any(axis=1))
+    return x0, y0, w, h
+
+
 def life_like_np(cells: np.ndarray, birth: int, survive: int, turns: int = 1) -> np.ndarray:
     """`turns` turns of the Life-like rule (birth, survive) on a torus of 0/255
     bytes: bit n of `birth` brings a dead cell with n alive neighbours (of 8)
@@ -1300,6 +1412,7 @@ def stamp_np(board_cells, cells, x0: int, y0: int, op: int = STAMP_COPY) -> np.n
 # --------------------------------------------------------------------------
 HOST_LIB_PATH = os.environ.get("GOLHOST_LIB") or os.path.join(HERE, "libgolhost.so")  # A/B builds
 FLAG_KEYS, FLAG_REF_QUIRKS, FLAG_NO_CELL_EVENTS, FLAG_NO_TURN_EVENTS, FLAG_VIEW_STRIPS = 0x1, 0x2, 0x4, 0x8, 0x10
+FLAG_SAVE_RLE = 0x20  # GOLRUN_FLAG_SAVE_RLE
 ALIVE_CELLS_COUNT, IMAGE_OUTPUT_COMPLETE, STATE_CHANGE, CELL_FLIPPED, TURN_COMPLETE, FINAL_TURN_COMPLETE = range(6)
 PAUSED, EXECUTING, QUITTING = range(3)
 EVENT_NAMES = ["AliveCellsCount", "ImageOutputComplete", "StateChange", "CellFlipped", "TurnComplete",
@@ -1371,7 +1484,7 @@ class Run:
                  keys: bool = False, quirks: bool = False, cell_events: bool = True, turn_events: bool = True,
                  events_cap: int = 0, ticker_ms: int = 0, view: dict | None = None, checkpoint: dict | None = None,
                  resume: str | None = None, stream_images: bool = False, image_every: int = 0, blank: bool = False,
-                 patterns=None, rule=None):
+                 patterns=None, rule=None, save_rle: bool = False):
         """view: the live view (golrun_start_view), dict(scale=..., every=1,
         x0=0, y0=0, out_w=None, out_h=None, fmt=VIEW_ARGB, strips=False);
         missing out_w / out_h are the largest that fit.  Run.view_frame()
@@ -1390,7 +1503,10 @@ class Run:
         "copy", "or" (the default), "xor" or "clear" (or a STAMP_* number).
         rule: the run's Life-like rule, "B36/S23" or (birth, survive) masks
         (None: Conway's); a resumed run names it again, pattern files must
-        name it or none."""
+        name it or none.  save_rle: beside the final image and the images of
+        `s` and `q`, out/<W>x<H>x<turn>.rle with the alive box of the board
+        (golhip_save_rle), complete before that image's ImageOutputComplete; an
+        empty board writes none."""
         lib = load_host()
         rule_word = 0
         if rule is not None:
@@ -1399,7 +1515,8 @@ class Run:
                 raise ValueError("rule masks above 0x1FF")
             rule_word = 0 if (rb, rs) == CONWAY else 0x40000 | rs << 9 | rb
         flags = (FLAG_KEYS if keys else 0) | (FLAG_REF_QUIRKS if quirks else 0) | \
-            (0 if cell_events else FLAG_NO_CELL_EVENTS) | (0 if turn_events else FLAG_NO_TURN_EVENTS)
+            (0 if cell_events else FLAG_NO_CELL_EVENTS) | (0 if turn_events else FLAG_NO_TURN_EVENTS) | \
+            (FLAG_SAVE_RLE if save_rle else 0)
         more = checkpoint is not None or resume is not None or stream_images or image_every != 0 or blank or \
             bool(patterns) or rule_word != 0  # golrun_start_opts
         spec = None

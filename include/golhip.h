@@ -40,6 +40,14 @@
  * (K1g, K1, K1w, the pair rule, K1r, K1p, the padded torus, K5, K5r), moved
  * the words per lane of a loaded board up and down, and put a stamp, a clear
  * and a step between a job's begin and its wait.
+ *
+ * Patterns go both ways: "patterns" below puts a rectangle of cells (bit
+ * words, an RLE file, a PGM) anywhere on the torus, "saving patterns" reads
+ * any rectangle back, finds the smallest box around the alive cells and writes
+ * either as an RLE file whose header names the board's rule -- the way to take
+ * home what a pattern became on a board too large to save as an image.  The
+ * model of oracle/ does not know the saving calls: they are observers, checked
+ * by tests/test_gpu_extract.py.
  */
 #ifndef GOLHIP_H
 #define GOLHIP_H
@@ -758,6 +766,68 @@ int golhip_pattern_rule(const char *path, uint32_t *birth, uint32_t *survive);
  * any other is GOLHIP_EINVAL with a message naming both rules. */
 int golhip_stamp_file(golhip_t *hs, int32_t n, const char *path, int32_t x0, int32_t y0, int32_t op,
                       golhip_pattern_info_t *info);
+
+/* ---- saving patterns ---------------------------------------------------- */
+/* The way back: any rectangle of the torus as bit words, the smallest box
+ * around the alive cells, and an RLE file of either.  The
+ * extract (K12) and the occupancy pass (K13) read the board on the device in
+ * the layout it is stepped in and never write it; results never depend on the
+ * words per lane, the strip count or the launch plan.
+ *
+ * golhip_extract_bits: the pw x ph cells whose top-left corner is the torus
+ * cell (x0, y0), as golhip_stamp_bits takes them: ph rows of ceil(pw / 32)
+ * uint32, pattern cell (r, c) = board cell ((y0 + r) mod height, (x0 + c) mod
+ * width), padding bits zero.  The requirements are the stamp's: 0 <= x0 <
+ * width, 0 <= y0 < height, 1 <= pw <= width, 1 <= ph <= height, a board
+ * loaded, no null pointer (GOLHIP_EINVAL); cap_words < ph * ceil(pw / 32) is
+ * GOLHIP_ERANGE.  On a strip handle y counts torus rows and the rows the strip
+ * does not own come back zero, as the stamp skips them (a rank of a ring is a
+ * strip like any other).  golhip_group_extract_bits reads the board held by
+ * the group of row strips golhip_group_step takes: every row of the rectangle
+ * comes from the strip that owns it.
+ *
+ * golhip_alive_box (hs, n: one whole-torus handle or a group of strips): the
+ * smallest box of at most one lap that holds every alive cell of the torus,
+ * seams included: a glider that has walked across both seams has a 3 x 3 box
+ * at (width - 1, height - 1).  Each side is golhip_box_interval of that axis'
+ * occupancy.  *pw = *ph = 0 (and *x0 = *y0 = 0) on an empty board.
+ *
+ * All three are observers: the board, the turn, the kept count and the kept
+ * flip list stay; they run behind whatever is enqueued on the handles' streams
+ * and synchronise them.
+ *
+ * golhip_box_interval (no device; exposed for tests): `bits` is the occupancy
+ * bitmap of a cyclic axis of n >= 1 positions (position p = bit p % 32 of word
+ * p / 32).  (*start, *len) is the shortest cyclic interval that covers every
+ * set bit, the complement of the longest cyclic run of clear bits; where
+ * several runs tie for longest, the interval with the smallest start.  No set
+ * bit: (0, 0).  No clear bit: (0, n). */
+int golhip_extract_bits(golhip_t h, int32_t x0, int32_t y0, int32_t pw, int32_t ph, uint32_t *words,
+                        uint64_t cap_words);
+int golhip_group_extract_bits(golhip_t *hs, int32_t n, int32_t x0, int32_t y0, int32_t pw, int32_t ph,
+                              uint32_t *words, uint64_t cap_words);
+int golhip_alive_box(golhip_t *hs, int32_t n, int32_t *x0, int32_t *y0, int32_t *pw, int32_t *ph);
+int golhip_box_interval(const uint32_t *bits, int32_t n, int32_t *start, int32_t *len);
+/* words as golhip_stamp_bits takes them -> an RLE file (no device): the line
+ * "#CXRLE Pos=<x0>,<y0> Gen=<turn>" (Golly's extended header; golhip_pattern_*
+ * skip '#' lines), "x = <pw>, y = <ph>, rule = <golhip_rule_format's
+ * spelling>", then the body in lines of at most 70 characters, counts of 1,
+ * trailing dead cells of a row and trailing dead rows left out, '!' at the
+ * end.  A pattern with no alive cell is the header and "!".  The file is
+ * written as <path>.tmp, fsynced and renamed over <path>; after a failure
+ * (GOLHIP_EINVAL, the message names the call that failed) no .tmp is left. */
+int golhip_pattern_write(const char *path, const uint32_t *words, int32_t pw, int32_t ph, uint32_t birth,
+                         uint32_t survive, int32_t x0, int32_t y0, int64_t turn);
+/* Box, extract and write in one call (hs, n: one whole-torus handle or a
+ * group of strips), chunk_rows rows at a time (0: the rows that fit 16 MiB of
+ * words, at least one): never more than one chunk is held on the host.  pw ==
+ * 0 && ph == 0: the alive box (x0, y0 ignored); an empty board is then
+ * GOLHIP_EINVAL "board is empty" and no file is written.  The header's rule
+ * is the handles' rule, Pos the box's corner, Gen the handles' turn.  info
+ * (nullable): width, height, alive as the writer counted them, format 0.  The
+ * file is committed as golhip_pattern_write commits it. */
+int golhip_save_rle(golhip_t *hs, int32_t n, const char *path, int32_t x0, int32_t y0, int32_t pw, int32_t ph,
+                    int32_t chunk_rows, golhip_pattern_info_t *info);
 
 /* ---- measurement ------------------------------------------------------ */
 int golhip_perf(golhip_t h, golhip_perf_t *out);

@@ -27,6 +27,14 @@ extern "C" {
 #define GOLRUN_FLAG_NO_TURN_EVENTS 0x8u  /* no per-turn TurnComplete                        */
 #define GOLRUN_FLAG_VIEW_STRIPS 0x10u    /* golrun_start_view: a run on row strips renders its
                                             view across them (golhip_group_view_frame)      */
+/* Bit 5, 0x20u: beside the final image and the images of `s` and `q` the run
+ * writes out/<W>x<H>x<turn>.rle, the alive box of the board at that turn
+ * (golhip_save_rle; one handle or strips), complete before that image's
+ * ImageOutputComplete; never transposed; an empty board writes no file and
+ * prints a line saying so; image_every images get none (gol_host.h
+ * RunOptions::save_rle; the environment's GOL_SAVE_RLE=1 does the same).
+ * golrun_opts_t has no free slot left, hence a flag bit. */
+#define GOLRUN_FLAG_SAVE_RLE (1u << 5)
 
 /* event kinds (gol/event.go) */
 #define GOLRUN_ALIVE_CELLS_COUNT 0

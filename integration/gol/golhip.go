@@ -105,6 +105,19 @@ package gol
 //                                golhip_pattern_info_t *info) {
 //     return gh_wrap(golhip_stamp_file(hs, n, path, x0, y0, op, info));
 // }
+// // Saving patterns (golhip_group_extract_bits, golhip_alive_box, golhip_save_rle):
+// // any rectangle read back, the box around the alive cells, an RLE file of either.
+// static gh_status gh_group_extract_bits(golhip_t *hs, int32_t n, int32_t x0, int32_t y0, int32_t pw, int32_t ph,
+//                                        uint32_t *words, uint64_t cap) {
+//     return gh_wrap(golhip_group_extract_bits(hs, n, x0, y0, pw, ph, words, cap));
+// }
+// static gh_status gh_alive_box(golhip_t *hs, int32_t n, int32_t *x0, int32_t *y0, int32_t *pw, int32_t *ph) {
+//     return gh_wrap(golhip_alive_box(hs, n, x0, y0, pw, ph));
+// }
+// static gh_status gh_save_rle(golhip_t *hs, int32_t n, const char *path, int32_t x0, int32_t y0, int32_t pw,
+//                              int32_t ph, int32_t chunk_rows, golhip_pattern_info_t *info) {
+//     return gh_wrap(golhip_save_rle(hs, n, path, x0, y0, pw, ph, chunk_rows, info));
+// }
 // // Life-like rules (golhip_rule_parse, golhip_set_rule): the rule of the turns
 // // enqueued from now on, two 9-bit masks; every strip of a group gets the same.
 // static gh_status gh_rule_parse(const char *text, uint32_t *birth, uint32_t *survive) {
@@ -266,6 +279,46 @@ func (e *engine) StampFile(path string, x0, y0, op int) (width, height int, aliv
 	check(C.gh_stamp_file((*C.golhip_t)(unsafe.Pointer(&e.hs[0])), C.int32_t(len(e.hs)), cpath, C.int32_t(x0), C.int32_t(y0),
 		C.int32_t(op), &info))
 	return int(info.width), int(info.height), uint64(info.alive)
+}
+
+// ExtractBits reads the pw x ph cells whose top-left corner is the torus cell
+// (x0, y0), wrapping in x and y, as StampBits takes them: ph rows of
+// ceil(pw/32) words, padding bits zero (golhip_group_extract_bits).  The board
+// is not written; turn, count and flip list stay.
+func (e *engine) ExtractBits(x0, y0, pw, ph int) []uint32 {
+	if pw < 1 || ph < 1 {
+		panic("ExtractBits: sizes start at 1")
+	}
+	words := make([]uint32, ph*((pw+31)/32))
+	check(C.gh_group_extract_bits((*C.golhip_t)(unsafe.Pointer(&e.hs[0])), C.int32_t(len(e.hs)), C.int32_t(x0), C.int32_t(y0),
+		C.int32_t(pw), C.int32_t(ph), (*C.uint32_t)(unsafe.Pointer(&words[0])), C.uint64_t(len(words))))
+	return words
+}
+
+// AliveBox is the smallest box of at most one lap around every alive cell of
+// the torus, seams included; pw = ph = 0 on an empty board (golhip_alive_box).
+func (e *engine) AliveBox() (x0, y0, pw, ph int) {
+	var cx, cy, cw, ch C.int32_t
+	check(C.gh_alive_box((*C.golhip_t)(unsafe.Pointer(&e.hs[0])), C.int32_t(len(e.hs)), &cx, &cy, &cw, &ch))
+	return int(cx), int(cy), int(cw), int(ch)
+}
+
+// SaveRle writes the rectangle (pw = ph = 0: the alive box) as an RLE file
+// whose header names the run's rule, a chunk of rows at a time, and returns its
+// width, height and alive cells (golhip_save_rle).  ok is false, and no file is
+// written, where the alive box was asked for and the board is empty.
+func (e *engine) SaveRle(path string, x0, y0, pw, ph int) (width, height int, alive uint64, ok bool) {
+	if pw == 0 && ph == 0 {
+		if _, _, w, _ := e.AliveBox(); w == 0 {
+			return 0, 0, 0, false
+		}
+	}
+	cpath := C.CString(path)
+	defer C.free(unsafe.Pointer(cpath))
+	var info C.golhip_pattern_info_t
+	check(C.gh_save_rle((*C.golhip_t)(unsafe.Pointer(&e.hs[0])), C.int32_t(len(e.hs)), cpath, C.int32_t(x0), C.int32_t(y0),
+		C.int32_t(pw), C.int32_t(ph), 0, &info))
+	return int(info.width), int(info.height), uint64(info.alive), true
 }
 
 // imageBegin starts the image of the board at its current turn
