@@ -988,6 +988,11 @@ __device__ __forceinline__ void push_group_pr_hi(Lanes<WPL> &x0, Lanes<WPL> &x1,
     Shifted nx;
     unit_pr<D, (KQ + 0 + LO) & 1, WPL>(LO, x0, sh, st, x1, nx);
     sh = nx;
+    // B(LO) shifts the row that A(LO) has just written, and B(D - 1) the one
+    // that C(D - 2) has: that unit's last LUT must not sink down to the DPP
+    // move, which as inline assembly gets no hazard pad (from_left_lane_far;
+    // at D = 15 it did, in the drain loops of LO = 3 and 9: DESIGN.md §5.23)
+    __builtin_amdgcn_sched_barrier(0);
     static_for<D - LO>([&](auto t_tag) {
         constexpr int t = LO + decltype(t_tag)::value;
         parity_fix<2>();
@@ -999,6 +1004,7 @@ __device__ __forceinline__ void push_group_pr_hi(Lanes<WPL> &x0, Lanes<WPL> &x1,
             unit_pr<D, (KQ + 2 + t) & 1, WPL>(t, x2, sh, st, x1, nx);
             sh = nx;
         } else {
+            __builtin_amdgcn_sched_barrier(0);
             unit_pr<D, (KQ + 1 + t) & 1, WPL>(t, x1, sh, st, x2, nx);
             sh = nx;
             xn = vmov_even(n0);
@@ -1168,7 +1174,9 @@ __device__ __forceinline__ uint32_t stream_skew(const StepArgs &a, int ab, int e
     [[maybe_unused]] unsigned long long wt0 = 0, wmain = 0, nmain = 0, wfill = 0, nfill = 0;
     auto fill = [&](auto a_tag) {
         constexpr int A = decltype(a_tag)::value;
-        for (; A == D ? k <= 2 * D - 1 : (k + 2) / 2 <= A - 1; k += 3) {
+        // (the pair rule at D = 16: one more full-depth group, so that the main loop starts at an even one)
+        constexpr int KFILL = skew_main_start(D, PR) != skew_main_start(D) ? skew_main_start(D, PR) - 1 : 2 * D - 1;
+        for (; A == D ? k <= KFILL : (k + 2) / 2 <= A - 1; k += 3) {
             const Lanes<WPL> n0 = load_next(), n1 = load_next(), n2 = load_next();
             __builtin_amdgcn_sched_barrier(0);
             Lanes<WPL> y0 = x0, y1 = x1, y2 = x2;
@@ -1275,7 +1283,7 @@ __device__ __forceinline__ uint32_t stream_skew(const StepArgs &a, int ab, int e
         // mod 6), other bands are multiples of 6 rows (gol_skew_kernel), so
         // the loop ends exactly at kmain where a drain follows; a stack's
         // bottom band may run up to 5 rows past its end (masked stores)
-        constexpr int KSTART = skew_main_start(D);
+        constexpr int KSTART = skew_main_start(D, PR);
         static_assert(KSTART % 6 == 0, "the pair main loop starts at an even push");
         {
             pr_enter<D, 0, WPL>(h0, h1, cc, st);
@@ -2328,6 +2336,8 @@ static hipError_t dispatch_skew(int depth, int wpl, bool half, bool pr, F &&f) {
     GOL_WCASE(9, 4) GOL_WCASE(16, 1) GOL_WCASE(32, 1)
     GOL_HCASE(16, 2) GOL_HCASE(20, 2)
     GOL_RCASE(18, 2, false) GOL_RCASE(18, 2, true) GOL_RCASE(8, 4, false)
+    // a whole torus' remainder launches (golhip_plan.cpp depth_plan): the pair rule at 12, 15 and 16 turns
+    GOL_RCASE(12, 2, false) GOL_RCASE(15, 2, false) GOL_RCASE(16, 2, false)
 #undef GOL_WCASE
 #undef GOL_HCASE
 #undef GOL_RCASE

@@ -31,6 +31,16 @@ namespace golk {
 constexpr int skew_phase_step(int D) { return D > 20 ? 6 : 3; }
 // The main loop's first push: the fill ends at 2 D, rounded to a whole group.
 constexpr int skew_main_start(int D) { return 3 * ((2 * D + 2) / 3); }
+// The pair rule's main loop takes two groups a body and so starts at an even
+// group: where the fill would end on an odd one (D = 16: push 33) its last
+// phase runs one more full-depth group (36).  The other pair depths (8, 12,
+// 15, 18) end their fill on an even group already.
+constexpr int skew_main_start(int D, bool pair) {
+    return pair ? 6 * ((skew_main_start(D) + 5) / 6) : skew_main_start(D);
+}
+// The pair-rule depths at two words per lane on full-width tiles that only a
+// whole torus' step plan asks for (golhip_plan.cpp depth_plan), beside 18.
+constexpr bool skew_pair_tail_depth(int D) { return D == 12 || D == 15 || D == 16; }
 // The main loop's end: the drain of a band with a band below it in the stack
 // starts at its first phase; a stack's bottom band (`self`) runs to the end.
 constexpr int skew_main_end(int S, int D, bool self) { return S + (self ? 2 * D : 2 * skew_phase_step(D)); }
@@ -67,7 +77,10 @@ GOL_SPAN_FN SkewBand skew_band(int L, int nst, int stack, int sy, int pos, const
 // launch: 65536^2 and every strip of that width).  The others measured no gain
 // or a loss (half-wave tiles, whose bands are mostly ramps,
 // and quads at 9) and keep the one general loop; their spans are empty.
-constexpr bool skew_interior_instance(int D, int wpl, bool half, bool pair) { return pair && wpl == 2 && !half && D == 18; }
+// The remainder launches of such a torus (12, 15 and 16 turns) carry it too.
+constexpr bool skew_interior_instance(int D, int wpl, bool half, bool pair) {
+    return pair && wpl == 2 && !half && (D == 18 || skew_pair_tail_depth(D));
+}
 
 struct SkewSpan {
     int k_lo, k_hi;  // the interior bodies are those at pushes [k_lo, k_hi): k_lo = k_hi if there are none
@@ -123,7 +136,7 @@ GOL_SPAN_FN SkewSpan skew_interior_span(const SkewSpanIn &in) {
     using namespace span_detail;
     const int B = in.pair ? 6 : 3;
     const int S = in.eb - in.ab, D = in.D;
-    const int k0 = skew_main_start(D);
+    const int k0 = skew_main_start(D, in.pair);
     SkewSpan none = {k0, k0};
     if (!in.enabled || in.counts || S <= 0 || S > 0x7FFFFFFF - 4 * D - 64) return none;
     // the bodies whose stores are all real: 0 <= k - 3 - 2 D and k - 4 - 2 D + B < S, within the loop
@@ -135,7 +148,9 @@ GOL_SPAN_FN SkewSpan skew_interior_span(const SkewSpanIn &in) {
     const int kmain = skew_main_end(S, D, in.self);
     int lo = 2 * D + 3, hi = S + 2 * D + 4 - B;  // k in [lo, hi)
     if (hi > kmain) hi = kmain;
-    if (lo < k0) lo = k0;
+    // (and the rows a body stores are the group's before it, which the main loop must have run: its first body
+    // stores nothing, the fill has stored its own groups' rows; only the pair rule at D = 16 starts past 2 D + 3)
+    if (lo < k0 + 3) lo = k0 + 3;
     const int K0 = k0 + (lo - k0 + B - 1) / B * B;
     if (hi <= K0) return none;
     const int K1 = K0 + (hi - K0 + B - 1) / B * B;  // one past the last body that starts below hi

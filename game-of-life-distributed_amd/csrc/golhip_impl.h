@@ -62,6 +62,9 @@ int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 // exactly 9 (depth_cap); see max_depth_for).
 constexpr int kDepths[] = {32, 24, 20, 18, 16, 12, 9, 8, 6, 4, 2, 1};
 constexpr int kNumDepths = sizeof(kDepths) / sizeof(kDepths[0]);
+// 15 turns: the pair-rule K1w alone, and only in a whole torus' planned tail
+// (depth_plan with pair_tail); it has the per-depth caches' last slot.
+constexpr int kDepthSlots = kNumDepths + 1;
 // trace buffer: 8 totals + (start, end) per (workgroup < 1024, wave < 64)
 constexpr int64_t kTraceWords = 8 + 2 * 1024 * 64;
 
@@ -165,9 +168,10 @@ struct golhip {
     int lds_bpc[4] = {};               // K1r workgroups per CU by (wpl, 512 / 1024 threads) at lds_bpc_bytes of LDS
     int64_t lds_bpc_bytes[4] = {};
     int lds_bpc_stride[4] = {};
-    int skew_bpc[gh::kNumDepths][12] = {};  // K1w workgroups per CU by (depth, wpl, half, pairs) (0: not queried)
+    int skew_bpc[gh::kDepthSlots][12] = {};  // K1w workgroups per CU by (depth, wpl, half, pairs) (0: not queried)
     int skew_pairs = 5;             // option "skew_pairs": the pair rule (8 LUTs a word-turn) at depth 18 (depth_cap)
-    int skew_interior = 1;          // option "skew_interior": K1w's interior main-loop body (gol_skew_span.h; 0: the general body alone)
+    bool pair_tail_step = false;    // the step in flight plans its tail from the pair depths 12 / 15 / 16 (pair_tail_on; skew_dims)
+    int skew_interior = 1;         // option "skew_interior": K1w's interior main-loop body (gol_skew_span.h; 0: the general body alone)
     unsigned *skew_err = nullptr;      // host-mapped spin-bound flag of the K1w kernels
     unsigned *skew_err_dev = nullptr;
     int lds_band = -1;              // option "lds_band": resident LDS bands K1r (1 on where it fits, 0 off, -1 auto)
@@ -209,7 +213,7 @@ struct golhip {
     int resident_max = (int)golk::kResidentMaxTurns;  // turns a resident launch takes (test hook "resident_max_turns")
     int64_t persist_fallbacks = 0;
     int64_t persist_timeout_ticks = 100000000ll;  // 1 s at the 100 MHz s_memrealtime clock (option "persist_timeout_us")
-    int auto_rpw[gh::kNumDepths] = {};  // cache per depth index
+    int auto_rpw[gh::kDepthSlots] = {};  // cache per depth index
     bool loaded = false;
     int il = 0;                 // word layout of the board: 0 canonical, 2 interleaved pairs, 4 quads (= wpl)
     std::atomic<int64_t> turns{0};
@@ -348,7 +352,8 @@ struct HaloRun {
     int d, k;
 };
 int largest_depth(int64_t want);
-DepthRun depth_plan(int cap, int64_t left);
+DepthRun depth_plan(int cap, int64_t left, bool pair_tail = false);
+bool pair_tail_on(golhip_t h);
 int sched_rows(golhip_t h);
 int persist_nw_for(golhip_t h, int depth, int wpl);
 bool persist_on(golhip_t h);

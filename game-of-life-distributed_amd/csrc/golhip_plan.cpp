@@ -28,11 +28,57 @@ static bool special_depth(int d) { return d == 9 || d == 18; }
 // end the run is `cap` turns; the last 12-13 caps are planned exactly
 // (262144^2 x 100 turns at cap 9: 4 x 9 + 8 x 8, not 8 x 9 + 2 x 8 + 2 x 6,
 // which a plan of only the last 3-4 caps found).
-DepthRun depth_plan(int cap, int64_t left) {
+//
+// pair_tail (a whole torus on the pair rule's full-width tiles, pair_tail_on):
+// the planned tail may also take the pair kernel's own remainder depths (12,
+// 15, 16), and the schedule is the one of least estimated cost, a launch of d
+// turns costing (d + r) x slots(d): r turns' worth of ramps, 12 issue slots a
+// word-turn on the pair rule and 13 on the 9-LUT stages.
+// The fewest-launches schedule stays wherever the estimate finds nothing
+// cheaper, its 12s and 16s on the pair kernel: 1,000 turns run 52 x 18 + 4 x 16
+// as before, 999 run 53 x 18 + 3 x 15 where they ran 55 x 18 + 8 + 1.
+static constexpr int kPairTailDepths[] = {18, 16, 15, 12, 8, 6, 4, 2, 1};
+// r in tenths of a turn, fitted to the 18-turn pair launch and the 16-turn
+// 9-LUT launch of profiles/pair_tail/step0_kernel_trace.json
+static constexpr int kRampTenths = 281;
+static int64_t launch_cost(int d, bool pair_kernel) { return (int64_t)(10 * d + kRampTenths) * (pair_kernel ? 12 : 13); }
+static bool pair_tail_depth(int d) { return d == 18 || golk::skew_pair_tail_depth(d); }
+
+static DepthRun first_run(std::vector<int> &seq, int M, int64_t head) {
+    std::sort(seq.begin(), seq.end(), std::greater<int>());
+    const int d = head > 0 ? M : seq[0];
+    int64_t n = head;
+    for (int x : seq) n += (x == d);
+    return {d, n};
+}
+
+DepthRun depth_plan(int cap, int64_t left, bool pair_tail) {
     const int M = special_depth(cap) ? cap : largest_depth(std::max(1, cap));  // 9: quads, 18: pairs (depth_cap)
     if (left <= 0) return {M, 0};
     const int64_t head = std::max<int64_t>(0, left / M - 12);  // launches of M before the planned tail
     const int t = (int)(left - head * M);                      // < 13 M <= 416
+    std::vector<int> cheap;
+    int64_t cheap_cost = -1;
+    if (pair_tail && M == 18) {
+        // least cost; then fewest launches, then the largest smallest launch
+        std::vector<int64_t> cost(t + 1, INT64_MAX);
+        std::vector<int> nl(t + 1, 0), mn(t + 1, INT_MAX), pick(t + 1, 0);
+        cost[0] = 0;
+        for (int v = 1; v <= t; ++v)
+            for (int d : kPairTailDepths) {
+                if (d > v) continue;
+                const int64_t c = cost[v - d] + launch_cost(d, pair_tail_depth(d));
+                const int n = nl[v - d] + 1, m = std::min(mn[v - d], d);
+                if (c < cost[v] || (c == cost[v] && (n < nl[v] || (n == nl[v] && m > mn[v])))) {
+                    cost[v] = c;
+                    nl[v] = n;
+                    mn[v] = m;
+                    pick[v] = d;
+                }
+            }
+        for (int v = t; v > 0; v -= pick[v]) cheap.push_back(pick[v]);
+        cheap_cost = cost[t];
+    }
     // best[v] = (launches, -smallest launch) for v turns; pick[v] = first depth
     std::vector<int> nl(t + 1, INT_MAX), mn(t + 1, 0), pick(t + 1, 0);
     nl[0] = 0;
@@ -49,11 +95,13 @@ DepthRun depth_plan(int cap, int64_t left) {
         }
     std::vector<int> seq;
     for (int v = t; v > 0; v -= pick[v]) seq.push_back(pick[v]);
-    std::sort(seq.begin(), seq.end(), std::greater<int>());
-    const int d = head > 0 ? M : seq[0];
-    int64_t n = head;
-    for (int x : seq) n += (x == d);
-    return {d, n};
+    if (cheap_cost >= 0) {
+        // ties keep that schedule (its 12s and 16s run on the pair kernel here too)
+        int64_t c = 0;
+        for (int x : seq) c += launch_cost(x, pair_tail_depth(x));
+        if (cheap_cost < c) return first_run(cheap, M, head);
+    }
+    return first_run(seq, M, head);
 }
 
 // Rows the launch schedule (depth, exchange depth, words per lane) is derived
@@ -221,7 +269,7 @@ int next_depth(golhip_t h, int64_t remaining, bool halo) { return depth_plan(dep
 static int depth_index(int d) {
     for (int i = 0; i < kNumDepths; ++i)
         if (kDepths[i] == d) return i;
-    return kNumDepths - 1;
+    return d == 15 ? kNumDepths : kNumDepths - 1;  // (15: the pair rule's remainder depth, kDepthSlots)
 }
 
 // Per-launch kernel with paired bands (gol_tb_pair_kernel; needs the fill skip).
@@ -276,11 +324,13 @@ static int skew_bpc(golhip_t h, int depth, int wpl, bool half, bool pr) {
 
 // The stack plan of a K1w launch over L rows: tiles, workgroup shape, stacks
 // and tile kind (no side effects); false if K1w does not apply.
-bool skew_dims(golhip_t h, int depth, int wpl, int L, golk::SkewArgs *sk) {
+static bool skew_dims_for(golhip_t h, int depth, int wpl, int L, bool tail, golk::SkewArgs *sk) {
     // the pair rule: 18 turns at two words per lane (option "skew_pairs" bit
     // 1; no other K1w runs 18: a strip whose group plans 18 without the bit
-    // takes the per-launch kernel), 8 at four (bit 2)
-    const bool pr = (depth == 18 && (h->skew_pairs & 1)) || (wpl == 4 && depth == 8 && (h->skew_pairs & 2));
+    // takes the per-launch kernel), 8 at four (bit 2); `tail`: 12, 15 and 16 at
+    // two, only in a step whose plan drew on them (depth_plan's pair_tail)
+    const bool pr = (depth == 18 && (h->skew_pairs & 1)) || (wpl == 4 && depth == 8 && (h->skew_pairs & 2)) ||
+                    (tail && wpl == 2 && golk::skew_pair_tail_depth(depth) && golk::skew_supported(depth, 2, false, true));
     if (!h->skew || h->W % 32 != 0 || !golk::skew_supported(depth, wpl, false, pr)) return false;
     const int hcap = h->skew_hcap >= 0 ? h->skew_hcap : 3 * depth / 4;
     const int smin = depth + 3;
@@ -330,6 +380,27 @@ bool skew_dims(golhip_t h, int depth, int wpl, int L, golk::SkewArgs *sk) {
     sk->nst = best_nst;
     sk->half = best_half;
     sk->hcap = hcap;
+    return true;
+}
+
+bool skew_dims(golhip_t h, int depth, int wpl, int L, golk::SkewArgs *sk) {
+    return skew_dims_for(h, depth, wpl, L, h->pair_tail_step, sk);
+}
+
+// Whether this handle's own steps plan their tail from the pair depths
+// (depth_plan's pair_tail): a whole torus stepped by itself whose K1w plan
+// runs the pair rule on full-width tiles (depth_cap's 18), with a stack plan
+// for every remainder instance too.  Rings, groups of strips, the wide board
+// of a padded torus, half-tile plans, quads and the Life-like rules are not.
+bool pair_tail_on(golhip_t h) {
+    if (!h->torus() || h->halo_mode() || h->rule_path() || !(h->skew_pairs & 1)) return false;
+    if (depth_cap(h, false) != 18) return false;  // (18 only ever with the pair rule on)
+    for (int d : {18, 16, 15, 12}) {
+        golk::SkewArgs sk{};
+        if (!golk::skew_supported(d, 2, false, true) || !skew_dims_for(h, d, 2, h->rows, true, &sk) || sk.half ||
+            !sk.pairs)
+            return false;
+    }
     return true;
 }
 
@@ -504,6 +575,20 @@ int golhip_halo_schedule(int32_t strip_rows, int32_t tb_depth, int32_t resident,
     return GOLHIP_OK;
 }
 
+int golhip_depth_schedule(int32_t cap, int32_t pair_tail, int64_t turns_left, int32_t *depth, int64_t *launches) {
+    if (!depth || !launches || cap < 1 || cap > GOLHIP_MAX_TB_DEPTH || turns_left < 1 || (pair_tail && cap != 18))
+        return fail(GOLHIP_EINVAL, "bad depth schedule request");
+    const DepthRun run = depth_plan(cap, turns_left, pair_tail != 0);
+    *depth = run.d;
+    *launches = run.n;
+    return GOLHIP_OK;
+}
+
+int64_t golhip_launch_cost(int32_t depth, int32_t pair_kernel) {
+    if (depth < 1 || depth > GOLHIP_MAX_TB_DEPTH) return -1;
+    return launch_cost(depth, pair_kernel != 0);
+}
+
 int golhip_skew_span(const golhip_skew_span_in_t *in, int32_t *k_lo, int32_t *k_hi) {
     if (!in || !k_lo || !k_hi || in->depth < 4 || in->depth > GOLHIP_MAX_TB_DEPTH || in->eb < in->ab || in->dr < 0 || in->row_words < 1)
         return fail(GOLHIP_EINVAL, "bad skew span request");
@@ -532,7 +617,11 @@ int golhip_skew_interior_plan(golhip_t h, int32_t depth, int32_t ext, int32_t co
     }
     golk::SkewArgs sk{};
     const int wpl = wpl_for(h);
-    if (!skew_plan(h, depth, wpl, a, &sk)) return GOLHIP_OK;  // no K1w launch at this depth: no bodies
+    // (a whole torus' own steps run 12 / 15 / 16 turns on the pair kernel)
+    h->pair_tail_step = !halo && ext == 0 && pair_tail_on(h);
+    const bool planned = skew_plan(h, depth, wpl, a, &sk);
+    h->pair_tail_step = false;
+    if (!planned) return GOLHIP_OK;  // no K1w launch at this depth: no bodies
     const int sy = 8 / sk.tx, L = sk.half ? a.rows_out / 2 : a.rows_out, B = sk.pairs ? 6 : 3;
     for (int stack = 0; stack < sk.nst; ++stack)
         for (int pos = 0; pos < sy; ++pos) {
@@ -540,7 +629,7 @@ int golhip_skew_interior_plan(golhip_t h, int32_t depth, int32_t ext, int32_t co
             const golk::SkewSpan s = golk::skew_interior_span(golk::SkewSpanIn{
                 b.ab, b.eb, depth, b.bottom, sk.pairs != 0, a.in.off, a.in.wrap, a.in.rmax, sk.half != 0, L, a.Ww,
                 counts != 0 && a.count_lo < a.count_hi, sk.interior != 0});
-            const int k0 = golk::skew_main_start(depth), k1 = golk::skew_main_end(b.eb - b.ab, depth, b.bottom);
+            const int k0 = golk::skew_main_start(depth, sk.pairs != 0), k1 = golk::skew_main_end(b.eb - b.ab, depth, b.bottom);
             *interior_bodies += (int64_t)(s.k_hi - s.k_lo) / B * sk.tiles_x;
             *main_bodies += (int64_t)(std::max(k1 - k0, 0) + B - 1) / B * sk.tiles_x;
         }

@@ -426,9 +426,17 @@ static int step_locked(golhip_t h, int64_t nturns, int32_t want_flips) {
         take_guard(h, &rc);
         if (rc) return rc;
     }
+    // a whole torus on the pair rule's full tiles plans its tail from the pair
+    // depths, and only then do 12 / 15 / 16 turns run on the pair kernel (skew_dims)
+    const bool pair_tail = !halo && left > tail && pair_tail_on(h);
+    struct TailFlag {
+        golhip_t h;
+        ~TailFlag() { h->pair_tail_step = false; }
+    } tail_flag{h};
+    h->pair_tail_step = pair_tail;
     while (left > tail) {
         if (!halo) {
-            const int d = depth_plan(depth_cap(h, false), left - tail).d;
+            const int d = depth_plan(depth_cap(h, false), left - tail, pair_tail).d;
             if (int rc = launch_depth(h, d, left - d == 0, false)) return rc;
             left -= d;
             continue;

@@ -368,6 +368,17 @@ int golhip_halo_plan(int32_t width, int32_t strip_rows, int32_t nranks, int32_t 
  * full-depth super-steps greedily instead of the balanced launch plan. */
 int golhip_halo_schedule(int32_t strip_rows, int32_t tb_depth, int32_t resident, int64_t turns_left,
                          int32_t *depth, int32_t *launches);
+/* The launch schedule of a step that is no strip's (exposed for tests): the
+ * next run of `launches` launches of `depth` turns for turns_left turns at
+ * most `cap` turns a launch, exactly as golhip_step plans it.  pair_tail != 0
+ * (cap 18 only): the plan of a whole torus on the pair rule's full-width
+ * tiles, whose last launches may take the pair kernel's remainder depths 12,
+ * 15 and 16 and are ranked by golhip_launch_cost; 0: every other plan. */
+int golhip_depth_schedule(int32_t cap, int32_t pair_tail, int64_t turns_left, int32_t *depth, int64_t *launches);
+/* That ranking's estimate of one launch of `depth` turns on the pair kernel
+ * (pair_kernel != 0) or on the 9-LUT stages: (depth + ramp) x issue slots a
+ * word-turn, in tenths of a turn-slot.  -1: bad depth. */
+int64_t golhip_launch_cost(int32_t depth, int32_t pair_kernel);
 /* The interior span of one band of a skewed-stack launch (exposed for tests;
  * DESIGN.md 5.20): the main-loop pushes [k_lo, k_hi), whole loop bodies, in
  * which the band's input rows [ab, eb) neither wrap (wrap; 0: no wrap) nor
