@@ -469,6 +469,9 @@ static int group_flip_generic(golhip_t *hs, int n, int64_t nturns, int format, v
         }
         counts[t] = c;
     }
+    // the turns ran as steps that keep their list; a flip stream keeps none
+    // (golhip_flips after it is GOLHIP_EINVAL, as after every other path of the stream)
+    for (int i = 0; i < n; ++i) hs[i]->flips_valid = false;
     *done_out = t;
     *total_out = t == 0 ? need : acc;
     return GOLHIP_OK;

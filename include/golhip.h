@@ -431,7 +431,10 @@ int golhip_alive_count_global(golhip_t h, uint64_t *count, int64_t *at_turn);
  * (x = col, y = row) pairs in global coordinates.  ERANGE sets *n.  The list
  * stays until the board is stepped, loaded, cleared or stamped: observers
  * (counts, snapshots, golhip_alive_cells, frames, checkpoints) keep it.
- * GOLHIP_EINVAL where the handle keeps no list of its current turn. */
+ * GOLHIP_EINVAL where the handle keeps no list of its current turn:
+ * golhip_step_flips and the flip streams (a group's, and those of a handle or
+ * a group with another rule than Conway's included) return their lists and
+ * keep none. */
 int golhip_flips(golhip_t h, int32_t *xy, uint64_t cap, uint64_t *n);
 /* Batched CellFlipped stream (distributor.go:93-173 with the per-turn
  * initializeAliveCells :212-220): advance nturns turns one at a time and

@@ -9,11 +9,12 @@ the GOLHIP_E* code that include/golhip.h documents, a driver draws calls from
 a weighted table with a seeded numpy generator, applies each to the model and
 to a target, and compares.
 
-* ``HandleModel`` -- the board as 0/255 bytes, the turn, the flip list (the two
-  boards it is the difference of), the jobs begun and not yet waited for.
-  Built from oracle.oracle (run_np, step_np, flips_np, alive_cells_np,
+* ``HandleModel`` -- the board as 0/255 bytes, the turn, the rule, the flip list
+  (the two boards it is the difference of), the jobs begun and not yet waited
+  for.  Built from oracle.oracle (run_np, step_np, flips_np, alive_cells_np,
   pack_bits, fill_random_np) and golhip's numpy restatements (stamp_np,
-  view_frame_np, board_hash_np, checkpoint_*_np).  Where the header is silent
+  view_frame_np, board_hash_np, checkpoint_*_np, life_like_np, extract_np,
+  alive_box_np, rle_parse_np, rle_format_np).  Where the header is silent
   the model says nothing: the flip list is then UNKNOWN and the driver does not
   ask for it.  Nothing here is copied from the library's host code.
 * ``BoardTarget`` / ``GroupTarget`` -- the same calls on a golhip.Board and on
@@ -30,6 +31,7 @@ one-line defect of the fake that the committed seeds must catch.
 from __future__ import annotations
 
 import os
+import re
 
 import numpy as np
 
@@ -39,6 +41,11 @@ from oracle.oracle import (alive_cells_np, fill_random_np, flips_np, pack_bits, 
 
 OK, EINVAL, ERANGE = 0, -1, -4
 UNKNOWN = "unknown"  # the header does not say whether the handle keeps a flip list
+CONWAY = (0x008, 0x00C)  # (birth, survive): bit n of each for n alive neighbours
+# the rules with a static instance of the rule kernel K11 besides Conway's, and three that take its dynamic policy
+STATIC_RULES = {"B36/S23": (0x048, 0x00C), "B3678/S34678": (0x1C8, 0x1D8), "B2/S": (0x004, 0x000),
+                "B3/S012345678": (0x008, 0x1FF), "B1357/S1357": (0x0AA, 0x0AA), "B36/S125": (0x048, 0x026)}
+DYNAMIC_RULES = {"B3578/S1246": (0x1A8, 0x056), "B0/S8": (0x001, 0x100), "B012345678/S": (0x1FF, 0x000)}
 
 
 class Refused(Exception):
@@ -106,6 +113,43 @@ def write_pgm(path: str, cells: Cells) -> None:
         f.write(pgm_bytes(cells.make()))
 
 
+def rule_text(rule) -> str:
+    """The canonical spelling of (birth, survive): "B36/S23", digits ascending."""
+    b, s = rule
+    return "B" + "".join(str(n) for n in range(9) if b >> n & 1) + "/S" + "".join(str(n) for n in range(9) if s >> n & 1)
+
+
+def rule_of_text(text: str):
+    """(birth, survive) of "B<digits>/S<digits>" (either case) or the legacy "<survive>/<birth>"."""
+    t = text.strip().upper()
+    if t.startswith("B"):
+        b, s = t[1:].split("/S")
+    else:
+        s, b = t.split("/")
+    return (sum(1 << int(c) for c in b), sum(1 << int(c) for c in s))
+
+
+_RLE_HEAD = re.compile(r"(?m)^(\s*x\s*=\s*\d+\s*,\s*y\s*=\s*\d+)\s*,\s*rule\s*=\s*(\S+)\s*$")
+
+
+def rle_split(text: str):
+    """(the rule an RLE text's header names or None, the text without it)."""
+    m = _RLE_HEAD.search(text)
+    if not m:
+        return None, text
+    return rule_of_text(m.group(2)), text[:m.start()] + m.group(1) + text[m.end():]
+
+
+def write_rle(path: str, cells: Cells, rule) -> None:
+    """An RLE file of the pattern whose header names `rule` (golhip_pattern_write; no device)."""
+    G.pattern_write(path, cells.make(), tuple(rule))
+
+
+def write_text(path: str, text: str) -> None:
+    with open(path, "w") as f:
+        f.write(text)
+
+
 def replay(target, method, *args, **kwargs):
     """One call as the driver makes it, and as its printed lines make it again:
     Cells arguments are built, and the answer is ("ok", value) or ("refused",
@@ -145,10 +189,31 @@ class HandleModel:
         self.njobs = 0
         self._count = None     # the fake's kept alive count
         self._behind = False   # the fake's defect "strip_behind"
+        self.rule = CONWAY     # (birth, survive) of the turns stepped from now on
+        self._lag = None       # the fake's defect "rule_lags_a_call": the rule the next stepping call still runs
 
     @property
     def nstrips(self) -> int:
         return 1 if self.cuts is None else len(self.cuts) - 1
+
+    # ---- the rule
+    def set_rule(self, rule):
+        b, s = rule
+        if not (0 <= b <= 0x1FF and 0 <= s <= 0x1FF):
+            raise Refused(EINVAL)  # the rule is then unchanged
+        if self.defect == "rule_lags_a_call" and (b, s) != self.rule:
+            self._lag = self.rule
+        if self.defect == "set_rule_drops_flips":
+            self.flip = None
+        self.rule = (int(b), int(s))  # board, turn, kept count, flip list and jobs stay
+
+    def _run(self, board, n, rule=None):
+        rule = rule or self._lag or self.rule
+        return self.run(board, n) if rule == CONWAY else G.life_like_np(board, rule[0], rule[1], n)
+
+    def _step1(self, board, rule=None):
+        rule = rule or self._lag or self.rule
+        return step_np(board) if rule == CONWAY else G.life_like_np(board, rule[0], rule[1], 1)
 
     # ---- board replaced
     def _replace(self, board, turn=0):
@@ -207,28 +272,43 @@ class HandleModel:
         elif self.defect != "flips_kept_over_stamp":
             self.flip = None
 
+    def stamp_file(self, path, x0, y0, op):
+        """golhip_stamp_file of an RLE file: it must name the handle's rule or
+        none (on a Conway handle that is golhip_pattern_info's check); then
+        the stamp of its cells."""
+        with open(path) as f:
+            named, text = rle_split(f.read())
+        if named is not None and named != self.rule and self.defect != "stamp_file_any_rule":
+            raise Refused(EINVAL)  # the board is then unchanged
+        cells = G.rle_parse_np(text)
+        self.stamp(cells, x0, y0, op)
+        return {"width": cells.shape[1], "height": cells.shape[0], "alive": int(cells.sum()), "format": "rle"}
+
     # ---- turns
     def _advance(self, n, want_flips=False):
         if n == 0:
             self.flip = UNKNOWN  # no turn was stepped: the header is silent
             return
         if want_flips:
-            prev = self.run(self.board, n - 1)
-            self.board = step_np(prev)
+            prev = self._run(self.board, n - 1)
+            self.board = self._step1(prev)
             self.flip = (prev, self.board)
         else:
-            self.board = self.run(self.board, n)
+            self.board = self._run(self.board, n)
             self.flip = None
         self.t += n
         self._count = None
 
     def step(self, n, want_flips=False):
         self._advance(n, want_flips)
+        if n > 0:
+            self._lag = None
 
     def _lists(self, n):
         b = self.board
+        rule = CONWAY if self.defect == "stream_steps_conway" else None
         for _ in range(n):
-            nb = step_np(b)
+            nb = self._step1(b, rule)
             yield nb, flips_np(b, nb)
             b = nb
 
@@ -239,6 +319,8 @@ class HandleModel:
             lists.append(l)
         self.board, self.t, self.flip = last, self.t + n, None if n > 0 else UNKNOWN
         self.fresh, self._count = self.fresh and n == 0, None
+        if n > 0:
+            self._lag = None
         xy = np.concatenate(lists).reshape(-1, 2) if lists else np.zeros((0, 2), np.int32)
         return (ERANGE if len(xy) > cap else OK, xy[:cap].astype(np.int32), [len(l) for l in lists], len(xy))
 
@@ -270,7 +352,11 @@ class HandleModel:
         if self.fresh and done != fit:
             raise SequenceMismatch(f"first flip batch on a replaced board ran {done} turns, {fit} of {n} fit in {cap}")
         self.fresh = False
+        before = boards[done - 2] if done > 1 else self.board
         self.board, self.t, self.flip, self._count = boards[done - 1], self.t + done, None, None
+        if self.defect == "rule_stream_keeps_flips" and self.cuts is not None and self.rule != CONWAY and done == n:
+            self.flip = (before, self.board)
+        self._lag = None
         xy = np.concatenate(lists[:done]).reshape(-1, 2)
         ent = _entries(xy, fmt, self.W)
         if self.defect == "stream_drops_last" and done < n and len(ent):
@@ -294,6 +380,8 @@ class HandleModel:
             frames.append(self._frame(self.board, view))
         if n - nf * every > 0 or n == 0:
             self._advance(n - nf * every)
+        if n > 0:
+            self._lag = None
         dt = np.uint8 if view[5] == G.VIEW_GRAY8 else np.uint32
         return (np.stack(frames) if frames else np.zeros((0, view[4], view[3]), dt), n)
 
@@ -359,6 +447,52 @@ class HandleModel:
 
     def view_frame(self, view):
         return (self._frame(self.board, view), self.t)
+
+    def _rect(self, x0, y0, w, h):
+        if not (0 <= x0 < self.W and 0 <= y0 < self.H and 1 <= w <= self.W and 1 <= h <= self.H):
+            raise Refused(EINVAL)
+
+    def extract(self, x0, y0, w, h):
+        self._rect(x0, y0, w, h)
+        cells = G.extract_np(self.board, x0, y0, w, h)
+        if self.defect == "extract_no_x_wrap" and x0 + w > self.W:
+            cells = cells.copy()
+            cells[:, self.W - x0:] = False
+        if self.defect == "extract_drops_flips":
+            self.flip = None
+        return cells
+
+    def alive_box(self):
+        if self.defect == "box_not_cyclic" and _alive(self.board):
+            ys, xs = np.nonzero(self.board == 255)
+            return (int(xs.min()), int(ys.min()), int(xs.max() - xs.min() + 1), int(ys.max() - ys.min() + 1))
+        return tuple(int(v) for v in G.alive_box_np(self.board))
+
+    def save_rle(self, path, box=None, chunk_rows=0):
+        """The info dict of the writer; the file itself is the driver's to check
+        (the fake writes it: the documented header lines and rle_format_np's body)."""
+        if box is None:
+            box = tuple(int(v) for v in G.alive_box_np(self.board))
+            if box[2] == 0:
+                raise Refused(EINVAL)  # an empty board: no file
+        self._rect(*box)
+        cells = G.extract_np(self.board, *box)
+        if self.fake:
+            rule = CONWAY if self.defect == "rle_names_conway" else self.rule
+            body = G.rle_format_np(cells).split("\n", 1)[1]
+            with open(path, "w") as f:
+                f.write(f"#CXRLE Pos={box[0]},{box[1]} Gen={self.t}\n"
+                        f"x = {box[2]}, y = {box[3]}, rule = {rule_text(rule)}\n{body}")
+        return {"width": box[2], "height": box[3], "alive": int(cells.sum()), "format": "rle"}
+
+    def split_rule(self, strip, rule, what, args):
+        """One strip of the group on another rule, one group call, the strip set
+        back: (the call's code, whether a file of its was written).  Every call
+        that takes a group refuses strips that disagree on the rule."""
+        if self.defect == "split_rule_steps" and what == "step":
+            self._advance(*args)
+            return (OK, False)
+        return (EINVAL, False)
 
     # ---- jobs in flight
     def _begin(self, kind, path):
@@ -547,6 +681,21 @@ class BoardTarget(_Target):
     def image_begin(self, path):
         return self._begin(_refusing(G.image_begin, self._handles(), path))
 
+    def set_rule(self, rule):
+        _refusing(self.b.set_rule, tuple(rule))
+
+    def stamp_file(self, path, x0, y0, op):
+        return _refusing(G.stamp_file, self._handles(), path, x0, y0, op)
+
+    def extract(self, x0, y0, w, h):
+        return _refusing(self.b.extract, x0, y0, w, h)
+
+    def alive_box(self):
+        return _refusing(self.b.alive_box)
+
+    def save_rle(self, path, box=None, chunk_rows=0):
+        return _refusing(G.save_rle, self._handles(), path, box, chunk_rows)
+
 
 class GroupTarget(_Target):
     """HandleModel's calls on the row strips [cuts[i], cuts[i + 1]) through the
@@ -664,12 +813,39 @@ class GroupTarget(_Target):
     def image_begin(self, path):
         return self._begin(_refusing(G.image_begin, self.bs, path))
 
+    def set_rule(self, rule):
+        _refusing(G.group_set_rule, self.bs, tuple(rule))
+
+    def stamp_file(self, path, x0, y0, op):
+        return _refusing(G.stamp_file, self.bs, path, x0, y0, op)
+
+    def extract(self, x0, y0, w, h):
+        return _refusing(G.group_extract, self.bs, x0, y0, w, h)
+
+    def alive_box(self):
+        return _refusing(G.group_alive_box, self.bs)
+
+    def save_rle(self, path, box=None, chunk_rows=0):
+        return _refusing(G.save_rle, self.bs, path, box, chunk_rows)
+
+    def split_rule(self, strip, rule, what, args):
+        old = self.bs[strip].rule()
+        _refusing(self.bs[strip].set_rule, tuple(rule))
+        try:
+            code = replay(self, what, *args)
+        finally:
+            _refusing(self.bs[strip].set_rule, old)
+        path = args[0] if what == "save_rle" else None
+        wrote = path is not None and (os.path.exists(path) or os.path.exists(path + ".tmp"))
+        return (OK if code[0] == "ok" else code[1], wrote)
+
 
 # --------------------------------------------------------------------------- the tables
 # (weight, kind).  A kind is a generator below: gen_<kind>(driver) -> (method, args, kwargs, pre).
 MUTATING = {"load_bytes", "load_bits", "fill_random", "clear", "checkpoint_load", "image_load", "stamp", "step",
-            "step_flips", "flip_stream", "view_stream"}
+            "step_flips", "flip_stream", "view_stream", "stamp_file", "split_rule"}
 STEPPING = {"step", "step_flips", "flip_stream", "view_stream"}
+REPLACING = {"load_bytes", "load_bits", "fill_random", "clear", "checkpoint_load", "image_load", "wpl"}
 
 TORUS_TABLE = [
     (3, "load_bytes"), (3, "load_bits"), (3, "fill_random"), (3, "clear"), (3, "checkpoint_load"), (2, "image_load"),
@@ -684,6 +860,21 @@ TORUS_TABLE = [
 ]
 # (golhip_step_flips has no group entry point; "persistent" and "lds_band" are accepted on strips and change nothing)
 GROUP_TABLE = [(w, k) for w, k in TORUS_TABLE if k != "step_flips"] + [(6, "stamp_strip")]
+
+# The tables of the "-rules" configurations: the old ones (left as they are: adding a kind
+# changes every draw of the sequences already committed) and the calls of the Life-like
+# rules and of the pattern savers.  Refused by the header: 12 + 4 of 167 by weight, and
+# the stamp_file draws whose file names another rule than the handle's.
+RULE_KINDS = [(12, "set_rule"), (5, "extract"), (3, "alive_box"), (6, "save_rle"), (8, "stamp_file"),
+              (2, "refused_set_rule"), (2, "refused_extract")]
+TORUS_RULES_TABLE = TORUS_TABLE + RULE_KINDS
+GROUP_RULES_TABLE = GROUP_TABLE + RULE_KINDS + [(12, "split_rule")]  # (seven group calls to draw from)
+TABLES = {None: (TORUS_TABLE, GROUP_TABLE), "rules": (TORUS_RULES_TABLE, GROUP_RULES_TABLE)}
+
+# what gen_set_rule draws: Conway's often enough that its kernel families still occur
+RULE_DRAWS = [CONWAY] * 4 + list(STATIC_RULES.values()) + list(DYNAMIC_RULES.values())
+HAND_RLES = ["x = 3, y = 3\nbo$2bo$3o!\n", "#C a glider\nx = 3, y = 3\nbo$\n2bo$ 3o !\n", "x = 4, y = 2\n4o$o2bo!\n",
+             "x = 5, y = 3\n!\n"]
 
 
 def table_kinds(table) -> list[str]:
@@ -705,9 +896,14 @@ class Driver:
         self.last_perf = None
         self.last_wpl = None
         self.lds_band = -1             # option "lds_band" as last accepted (its default: automatic)
+        self.rles: list[str] = []      # RLE files a save_rle of this sequence wrote
+        self.rules = any(k == "set_rule" for _, k in table)  # the "-rules" tables: their extra checks
+        self.since_wpl: set = set()    # accepted calls since words_per_lane was last read
+        self.rule_at_wpl = CONWAY
         w = np.array([x for x, _ in table], dtype=float)
         self.weights = w / w.sum()
-        for key, zero in (("kinds", {}), ("families", set()), ("wpl_moves", set()), ("jobs_between", [])):
+        for key, zero in (("kinds", {}), ("families", set()), ("wpl_moves", set()), ("jobs_between", []), ("notes", set()),
+                          ("rules_stepped", set()), ("rule_wpl_moves", set()), ("trail", [])):
             self.stats.setdefault(key, zero)
 
     # ---- drawing
@@ -891,6 +1087,99 @@ class Driver:
         n = every * self.pick([2, 3])
         return "view_stream", (n, every, self.view(), n // every - 1), {}, []
 
+    # ---- the kinds of the "-rules" tables
+    def rect(self):
+        """A rectangle biased as pattern() biases stamps; on a group half of those taller than a row span a cut."""
+        c, x0, y0 = self.pattern()
+        pw, ph = c.a[0], c.a[1]
+        m = self.model
+        if m.cuts is not None and ph > 1 and self.rng.random() < 0.5:
+            y0 = (self.pick(m.cuts[1:-1]) - int(self.rng.integers(1, ph))) % m.H
+        return x0, y0, pw, ph
+
+    def other_rule(self):
+        return self.pick([r for r in RULE_DRAWS if r != self.model.rule])
+
+    def gen_set_rule(self):
+        return "set_rule", (self.pick(RULE_DRAWS),), {}, []
+
+    def gen_extract(self):
+        return "extract", self.rect(), {}, []
+
+    def gen_alive_box(self):
+        return "alive_box", (), {}, []
+
+    def gen_save_rle(self):
+        box = None if self.rng.random() < 0.5 else self.rect()
+        return "save_rle", (self.path("rle"), box, self.pick([0, 1, 2, 7])), {}, []
+
+    def gen_stamp_file(self):
+        c, x0, y0 = self.pattern()
+        op = self.pick([0, 1, 2, 3])
+        how = self.pick(["saved", "saved", "written", "written", "hand"])
+        if how == "saved" and self.rles:  # a file of this sequence: its rule may or may not be today's
+            return "stamp_file", (self.pick(self.rles), x0, y0, op), {}, []
+        p = self.path("rle")
+        if how == "hand":  # names no rule: every handle takes it
+            return "stamp_file", (p, x0, y0, op), {}, [("write_text", (p, self.pick(HAND_RLES)))]
+        rule = self.model.rule if self.rng.random() < 0.5 else self.pick(RULE_DRAWS)
+        return "stamp_file", (p, x0, y0, op), {}, [("write_rle", (p, c, rule))]
+
+    def gen_refused_set_rule(self):
+        b, s = self.pick(RULE_DRAWS)
+        return "set_rule", (self.pick([(b | 0x200, s), (b, s | 0x200), (0x200, 0x200)]),), {}, []
+
+    def gen_refused_extract(self):
+        W, H = self.model.W, self.model.H
+        x0, y0, w, h = self.rect()
+        return "extract", self.pick([(W, y0, w, h), (x0, H, w, h), (-1, y0, w, h), (x0, y0, W + 1, h),
+                                     (x0, y0, w, H + 1), (x0, y0, 0, h), (x0, y0, w, 0)]), {}, []
+
+    def gen_split_rule(self):
+        """One strip on another rule, one group call (refused: EINVAL), the strip set back."""
+        m = self.model
+        what = self.pick(["step", "flip_stream", "view_frame", "stamp", "extract", "alive_box", "save_rle"])
+        if what == "step":
+            args = (self.pick([1, 2, self.depth + 1]),)
+        elif what == "flip_stream":
+            args = (self.pick([1, 3]), m.W * m.H, G.FLIPS_XY)
+        elif what == "view_frame":
+            args = (self.view(),)
+        elif what == "stamp":
+            c, x0, y0 = self.pattern()
+            args = (c, x0, y0, self.pick([0, 1, 2, 3]))
+        elif what == "extract":
+            args = self.rect()
+        elif what == "alive_box":
+            args = ()
+        else:
+            args = (self.path("rle"), self.pick([None, self.rect()]), 0)
+        return "split_rule", (int(self.rng.integers(m.nstrips)), self.other_rule(), what, args), {}, []
+
+    def saved(self, args, got):
+        """The file of a save_rle: its cells, its rule, its #CXRLE line; or no file at all."""
+        path, box, _ = args
+        m = self.model
+        if got[0] != "ok":
+            if os.path.exists(path) or os.path.exists(path + ".tmp"):
+                self.fail(f"save_rle: refused with {got[1]} and left {path} or its .tmp")
+            if box is None and not _alive(m.board):
+                self.stats["notes"].add("save_rle_empty")
+            return
+        box = box if box is not None else tuple(int(v) for v in G.alive_box_np(m.board))
+        with open(path) as f:
+            text = f.read()
+        named, bare = rle_split(text)
+        if os.path.exists(path + ".tmp"):
+            self.fail(f"save_rle: {path}.tmp is left")
+        if text.split("\n")[0] != f"#CXRLE Pos={box[0]},{box[1]} Gen={m.t}":
+            self.fail(f"save_rle: {path} begins {text[:60]!r}, the box is {box} and the turn {m.t}")
+        if named != m.rule or tuple(G.pattern_rule(path)) != m.rule:
+            self.fail(f"save_rle: {path} names the rule {named}, the handle has {m.rule}")
+        if not np.array_equal(G.rle_parse_np(bare), G.extract_np(m.board, *box)):
+            self.fail(f"save_rle: the cells of {path} are not the board's at {box}")
+        self.rles.append(path)
+
     # ---- applying
     def fail(self, what, got=None):
         m = self.model
@@ -945,6 +1234,8 @@ class Driver:
             self.call(m)
         if self.model.flip != UNKNOWN and self.rng.random() < 0.5:  # the list, or EINVAL, as the model says
             self.call("flips")
+        if self.rules:
+            self.call("alive_box")
 
     def full(self):
         m = self.model
@@ -955,6 +1246,11 @@ class Driver:
         r = int(self.rng.integers(rows))
         self.call("snapshot_rows", (r, int(self.rng.integers(0, rows - r + 1))), {} if strip is None else {"strip": strip})
         self.call("view_frame", ((0, 0, 1, m.W, m.H, G.VIEW_GRAY8),))
+        if self.rules:  # one drawn extract, and what an observer promises to leave: the kept count and the flip list
+            self.call("extract", self.rect())
+            self.call("alive_count")
+            if m.flip != UNKNOWN:
+                self.call("flips")
 
     def classify(self, method):
         """The kernel families a stepping call took, from the change in perf()."""
@@ -994,11 +1290,29 @@ class Driver:
             fam.add("K5")
         if d["flip_resident_launches"] > 0:
             fam.add("K5r")
+        rule = self.model.rule
+        if d["rule_launches"] > 0:  # the rule kernel K11: canonical words, any width
+            self.stats["rules_stepped"].add(rule)
+            if d["pad_launches"] > 0:
+                fam.add("K11-padded")
+            elif W % 32:
+                fam.add("K11-seam")
+            else:
+                fam.add("K11-static" if rule in STATIC_RULES.values() else "K11-dynamic")
+            if method in ("flip_stream", "step_flips") and d["flip_launches"] == 0 and d["flip_resident_launches"] == 0:
+                fam.add("K11-flips")
+        if d["rule_launches"] > 0:  # which kind of kernel each stepping call of the sequence ran on
+            self.stats["trail"].append("K11")
+        elif d["step_launches"] + d["persist_launches"] + d["flip_launches"] + d["flip_resident_launches"] > 0:
+            self.stats["trail"].append("Conway")
         if method in ("step", "view_stream") and W % 32 == 0 and d["step_turns"] + d["persist_turns"] > 0:
             wpl = p["words_per_lane"]
             if self.last_wpl is not None and wpl != self.last_wpl:
                 self.stats["wpl_moves"].add((self.last_wpl, wpl))
-            self.last_wpl = wpl
+                # a move that a set_rule made: the board was not replaced and option "wpl" not set in between
+                if rule != self.rule_at_wpl and "set_rule" in self.since_wpl and not self.since_wpl & REPLACING:
+                    self.stats["rule_wpl_moves"].add((self.last_wpl, wpl))
+            self.last_wpl, self.rule_at_wpl, self.since_wpl = wpl, rule, set()
 
     def finish_job(self, entry):
         job_t, job_m = entry[0]
@@ -1033,6 +1347,21 @@ class Driver:
                 self.stats["kinds"][kind] = self.stats["kinds"].get(kind, 0) + 1
             t_before = self.model.t
             got, want = self.call(method, args, kwargs, pre)
+            if method == "save_rle":
+                self.saved(args, got)
+            if method == "split_rule":
+                self.stats["notes"].add("split_rule:" + args[2])
+            if method == "stamp_file":
+                with open(args[0]) as f:
+                    named = rle_split(f.read())[0]
+                if got[0] == "ok":
+                    self.stats["notes"].add("stamp_file_accepted")
+                    if args[0] in self.rles:  # the writer's own header back through the library's parser
+                        self.stats["notes"].add("stamp_file_saved_accepted")
+                elif named is not None and named != self.model.rule:
+                    self.stats["notes"].add("stamp_file_refused_for_its_rule")
+            if isinstance(got, tuple) and got[0] == "ok":
+                self.since_wpl.add(args[0] if method == "set_option" else method)
             if method in ("checkpoint_begin", "image_begin"):
                 self.pending.append([(got, want), int(self.rng.integers(1, 7)), set()])
             else:
@@ -1066,9 +1395,16 @@ def run_sequence(target, model, rng, n_ops, table, tmpdir, stats=None, prefix=()
     alive_count() and board_hash() are compared; after every eighth call and at
     the end snapshot_bytes, snapshot_bits, snapshot_rows of a random interval,
     alive_cells and view_frame at scale 1 -- all by exact equality.  Raises
-    SequenceMismatch with the calls so far as Python lines.  `stats` collects
-    the call kinds drawn, the kernel families taken (from perf()), the moves of
-    words_per_lane and what fell between each job's begin and wait."""
+    SequenceMismatch with the calls so far as Python lines.  A table with the
+    kind "set_rule" (the "-rules" tables) adds alive_box() after every mutating
+    call and, after every eighth, one drawn extract with alive_count() and
+    flips() behind it; the first tables' sequences draw and compare what they
+    always did (tests/golden/sequence_lines_parent.json pins their lines).
+    `stats` collects the call kinds drawn, the kernel families taken (from
+    perf()), the moves of words_per_lane (and those a set_rule made), the rules
+    that stepped on K11, whether each stepping call ran on K11 or on a Conway
+    kernel, notes for the CPU coverage condition and what fell between each
+    job's begin and wait."""
     d = Driver(target, model, rng, table, tmpdir, stats, name)
     d.run(n_ops, prefix)
     return d
@@ -1092,7 +1428,24 @@ CONFIGS = {
                                           ("set_tb_depth", (16,), {}, []), ("step", (33, True), {}, [])]),
     "128x50-strips": dict(W=128, H=50, cuts=[0, 7, 17, 50]),
     "100x50-strips": dict(W=100, H=50, cuts=[0, 7, 17, 50]),
+    # the "-rules" tables (set_rule, the pattern savers) on the boards above
+    "128x17-rules": dict(W=128, H=17, table="rules", prefix=[("set_option", ("persistent", 1), {}, [])]),
+    "192x33-rules": dict(W=192, H=33, table="rules", prefix=[("set_option", ("persistent", 0), {}, [])]),
+    "100x37-rules": dict(W=100, H=37, table="rules"),
+    "33x9-rules": dict(W=33, H=9, table="rules"),
+    "128x130-rules": dict(W=128, H=130, table="rules",
+                          prefix=[("set_option", ("skew", 2), {}, []), ("set_option", ("persistent", 0), {}, []),
+                                  ("set_option", ("wpl", 2), {}, []), ("step", (41, False), {}, []),
+                                  ("set_tb_depth", (16,), {}, []), ("step", (33, True), {}, [])]),
+    "128x50-strips-rules": dict(W=128, H=50, table="rules", cuts=[0, 7, 17, 50]),
+    "100x50-strips-rules": dict(W=100, H=50, table="rules", cuts=[0, 7, 17, 50]),
 }
+
+
+def config_table(name):
+    """The table a committed configuration draws from: by its key "table", a torus' or a group's."""
+    c = CONFIGS[name]
+    return TABLES[c.get("table")][1 if c.get("cuts") else 0]
 
 
 def run_config(name, seed, tmpdir, target=None, stats=None, n_ops=40, **model_args):
@@ -1105,7 +1458,7 @@ def run_config(name, seed, tmpdir, target=None, stats=None, n_ops=40, **model_ar
     if own:
         target = BoardTarget(c["W"], c["H"]) if cuts is None else GroupTarget(c["W"], c["H"], cuts)
     try:
-        return run_sequence(target, model, np.random.default_rng(seed), n_ops, GROUP_TABLE if cuts else TORUS_TABLE,
+        return run_sequence(target, model, np.random.default_rng(seed), n_ops, config_table(name),
                             tmpdir, stats, c.get("prefix", ()), name="t")
     finally:
         if own:

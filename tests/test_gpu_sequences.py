@@ -20,8 +20,27 @@ The boards are the smallest at which each path exists:
   128 x 130  K1w (skew 2): rows for a stack of bands, 123 for the pair rule's 18 turns
   128 x 50 and 100 x 50 cut at 0, 7, 17, 50   strips on the fast kernels; padded and K1g strips
 
-and one more board for K1p alone (test_persistent_sequence).  The last test asserts
-that the committed seeds took every kernel family at least once.
+and one more board for K1p alone (test_persistent_sequence).  test_family_coverage
+asserts that these seeds took every kernel family at least once.
+
+The "-rules" configurations draw from the second pair of tables: the same calls
+and golhip_set_rule (Conway's, the six other rules with a static instance of
+the rule kernel K11, three that take its dynamic policy), extract, alive_box,
+save_rle, stamp_file and, on a group, one strip on another rule.  After every
+mutating call alive_box() is compared too, after every eighth one drawn extract
+and, behind it, the kept count and the kept flip list.
+
+  128 x 17   quads, pairs and K1r under Conway <-> canonical words under a rule, on
+             a loaded board, both ways; H just over K11's 16-turn cap
+  192 x 33   pairs <-> canonical words; no resident kernel
+  100 x 37   the padded torus with a rule: the wide board inherits the rule and
+             changes it between padded steps; set_pad_step 0: K11's one-turn seam form
+  33 x 9     one partial word and one whole word a row: K11's odd-width form only
+  128 x 130  K1w and the pair rule under Conway <-> K11
+  128 x 50 and 100 x 50 cut at 0, 7, 17, 50   group_set_rule, strips on K11, the
+             group observers, split_rule; padded strips with a rule
+
+test_rule_family_coverage is the condition over these seeds.
 """
 import numpy as np
 import pytest
@@ -45,8 +64,17 @@ SEEDS = {
     "128x130": [28, 29, 30],
     "128x50-strips": [10, 20, 21],
     "100x50-strips": [1, 12, 23],
+    "128x17-rules": [1, 2, 45],
+    "192x33-rules": [1, 45, 390],
+    "100x37-rules": [45, 146, 227],
+    "33x9-rules": [1, 2, 7],
+    "128x130-rules": [1, 2, 147],
+    "128x50-strips-rules": [35, 98, 185],
+    "100x50-strips-rules": [38, 66, 101],
 }
 CASES = [(name, seed) for name, seeds in SEEDS.items() for seed in seeds]
+OLD_CASES = [(name, seed) for name, seed in CASES if hm.CONFIGS[name].get("table") is None]
+RULE_CASES = [(name, seed) for name, seed in CASES if hm.CONFIGS[name].get("table") == "rules"]
 
 # K1p: with persistent 1 and lds_band 0, perf() showed persist_launches rising
 # without lds_launches on every square board probed (32, 64, 96, 128, 192, 256,
@@ -112,7 +140,7 @@ def test_persistent_sequence(tmp_path):
     assert "K1p" in stats["families"], stats["families"]
 
 
-# ---------------------------------------------------------------- the two findings, three calls each
+# ---------------------------------------------------------------- the findings, three to five calls each
 def test_flips_after_alive_cells():
     """golhip_alive_cells reuses the block counts of the flip list: the list
     stays valid (both boards of the difference are intact) and golhip_flips
@@ -154,11 +182,34 @@ def test_flip_stream_after_replaced_board(group):
         t.close()
 
 
+@pytest.mark.parametrize("group", [False, True])
+def test_no_flips_after_a_rule_flip_stream(group):
+    """A flip stream returns its lists and keeps none, whatever path it takes:
+    under another rule than Conway's a group's stream steps turn by turn with
+    kept lists, and golhip_flips after it must still be EINVAL."""
+    W, H, cuts = 128, 50, [0, 7, 17, 50]
+    m = hm.HandleModel(W, H, cuts if group else None)
+    t = hm.GroupTarget(W, H, cuts) if group else hm.BoardTarget(W, H)
+    try:
+        for x in (t, m):
+            x.fill_random(11)
+            x.set_rule(hm.STATIC_RULES["B36/S23"])
+        got = t.flip_stream(2, 2 * W * H, golhip.FLIPS_XY)
+        assert got[2] == 2 and hm.Driver.same(got, m.flip_stream(2, 2 * W * H, golhip.FLIPS_XY, done=got[2]))
+        for x in (t, m):
+            with pytest.raises(hm.Refused) as e:
+                x.flips()
+            assert e.value.code == hm.EINVAL
+        assert t.board_hash() == m.board_hash() and t.turn() == m.turn()
+    finally:
+        t.close()
+
+
 # ---------------------------------------------------------------- coverage over the committed seeds
 def test_family_coverage(tmp_path_factory):
     """A condition on the committed seeds, so that an edit of the tables cannot
     silently lose a kernel family."""
-    stats = [sequence(name, seed, tmp_path_factory.mktemp("s")) for name, seed in CASES]
+    stats = [sequence(name, seed, tmp_path_factory.mktemp("s")) for name, seed in OLD_CASES]
     stats.append(persistent_sequence(tmp_path_factory.mktemp("p")))
     families = set().union(*(s["families"] for s in stats))
     want = {"K1g", "K1", "K1w", "K1w-pair", "K1r", "K1p", "padded", "K5", "K5r"}
@@ -167,3 +218,26 @@ def test_family_coverage(tmp_path_factory):
     assert any(a < b for a, b in moves) and any(a > b for a, b in moves), moves
     assert {1, 2, 4} <= {w for m in moves for w in m}, moves
     assert any({"stamp", "clear", "step"} <= s for st in stats for s in st["jobs_between"])
+
+
+def test_rule_family_coverage(tmp_path_factory):
+    """The same over the seeds of the "-rules" configurations: every form of the
+    rule kernel, every static rule, the word layout converted by a set_rule both
+    ways, Conway's kernels and K11 in turn on one handle, a rule changed under a
+    job in flight."""
+    stats = [sequence(name, seed, tmp_path_factory.mktemp("r")) for name, seed in RULE_CASES]
+    families = set().union(*(s["families"] for s in stats))
+    want = {"K11-static", "K11-dynamic", "K11-seam", "K11-padded", "K11-flips"}
+    assert want <= families, f"never taken: {sorted(want - families)}"
+    stepped = set().union(*(s["rules_stepped"] for s in stats))
+    assert set(hm.STATIC_RULES.values()) <= stepped, f"never stepped: {set(hm.STATIC_RULES.values()) - stepped}"
+    moves = set().union(*(s["rule_wpl_moves"] for s in stats))
+    assert any(a in (2, 4) and b == 1 for a, b in moves) and any(a == 1 and b in (2, 4) for a, b in moves), moves
+
+    def in_turn(trail):  # a Conway family, then K11, then a Conway family again
+        i = trail.index("Conway") if "Conway" in trail else len(trail)
+        j = trail.index("K11", i) if "K11" in trail[i:] else len(trail)
+        return "Conway" in trail[j:]
+
+    assert any(in_turn(s["trail"]) for s in stats), [s["trail"] for s in stats]
+    assert any({"set_rule", "step"} <= s for st in stats for s in st["jobs_between"])
