@@ -472,6 +472,13 @@ struct RunOptions {
     struct Rule {
         uint32_t birth = 0x008, survive = 0x00C;
     } rule;
+    // The flip streams of a run with another rule than Conway's on the fused
+    // turn + list kernel K14 (golhip_set_rule_flips 1 on every handle, right
+    // after the rule): one launch a turn instead of a step, a compaction and
+    // two synchronisations.  The events are the same either way; a Conway run
+    // ignores it.  Opt-in: 1 on, 0 off, -1 from the environment,
+    // GOL_RULE_FLIPS=1 (unset: off).
+    int rule_flips = -1;
 };
 
 // One "path@x,y[,op]" (op: copy | or | xor | clear, default or), as the

@@ -134,6 +134,31 @@ struct DynRule {
     }
 };
 
+// The whole turn of one word from three rows' words x with their west (w, bit
+// b = cell b - 1) and east (e, bit b = cell b + 1) neighbours already aligned,
+// as the fused turn + list kernel K14 has them (gol_rule_flip.hip): the row
+// sums h0 + 2 h1 with K1's two LUTs, the column sums u and v, rule_t and the
+// policy's next with the middle row's word as the centre.  6 + 4 + 3 LUTs and
+// the policy's 5 (StaticRule: 18 a word) or 17 (DynRule: 30).
+constexpr unsigned kRuleXor3 = 0x96;  // a ^ b ^ c
+constexpr unsigned kRuleMaj = 0xE8;   // a + b + c >= 2
+template <class Ops, class Rule>
+GOL_RULE_HD uint32_t rule_next_words(const Rule &rule, const uint32_t (&w)[3], const uint32_t (&x)[3],
+                                     const uint32_t (&e)[3]) {
+    uint32_t h0[3], h1[3];
+    for (int j = 0; j < 3; ++j) {
+        h0[j] = Ops::template op<kRuleXor3>(w[j], x[j], e[j]);
+        h1[j] = Ops::template op<kRuleMaj>(w[j], x[j], e[j]);
+    }
+    const uint32_t u0 = Ops::template op<kRuleXor3>(h0[0], h0[1], h0[2]);
+    const uint32_t u1 = Ops::template op<kRuleMaj>(h0[0], h0[1], h0[2]);
+    const uint32_t v0 = Ops::template op<kRuleXor3>(h1[0], h1[1], h1[2]);
+    const uint32_t v1 = Ops::template op<kRuleMaj>(h1[0], h1[1], h1[2]);
+    uint32_t t0, t1, t2;
+    rule_t<Ops>(u1, v0, v1, t0, t1, t2);
+    return rule.template next<Ops>(u0, t0, t1, t2, x[1]);
+}
+
 // The rules with a static instantiation (launch_step_rule picks the dynamic
 // policy for every other): name, birth, survive.
 #define GOL_STATIC_RULES(X)            \

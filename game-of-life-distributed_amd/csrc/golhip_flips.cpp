@@ -212,7 +212,10 @@ static int flip_turn_launch(golhip_t h, const FlipBatch &b, int64_t t, bool over
     a.coresident = b.coresident ? 1 : 0;
     a.alive = last ? h->d_scalars : nullptr;
     if (int rc = span_begin(h, h->stream)) return rc;
-    HIP_OR_FAIL(golk::launch_flip_turn(a, h->stream));
+    if (h->rule_path())  // (here only with golhip_set_rule_flips 1: K14)
+        HIP_OR_FAIL(golk::launch_rule_flip_turn(a, h->birth, h->survive, h->rule_kernel == 2, h->stream));
+    else
+        HIP_OR_FAIL(golk::launch_flip_turn(a, h->stream));
     if (int rc = span_end(h, 2)) return rc;
     h->n.flip_launches++;
     h->cur ^= 1;
@@ -279,7 +282,10 @@ static int flip_stream_locked(golhip_t h, int64_t nturns, int format, void *out,
     const int64_t t0 = h->turns;
     const int c0 = h->cur;
 
-    if (nw >= (1ll << 32) - 4096 || h->rule_path()) return flip_generic(h, b, done_out, total_out);
+    if (nw >= (1ll << 32) - 4096 || !h->fused_flips()) return flip_generic(h, b, done_out, total_out);
+    // a rule handle here (golhip_set_rule_flips 1) runs K14, K5's per-launch kernel with the rule as a
+    // policy: everything below holds for it, with its own occupancy and no resident form
+    const bool k14 = h->rule_path();
 
     // fused turn + list (K5) on the canonical layout, at any width (W % 32 != 0:
     // the kernel closes the row seam itself, no padded torus); into a golhip_host_alloc
@@ -293,7 +299,10 @@ static int flip_stream_locked(golhip_t h, int64_t nturns, int format, void *out,
     void *direct = b.direct = mapped_device_ptr(out, (size_t)dcap * esz);
     const int64_t nb = b.nb = golk::flip_turn_blocks(nw);
     const bool contig = h->Ww % 4 == 0;
-    const int bpc = std::min(golk::flip_turn_blocks_per_cu(contig, h->W % 32 != 0), 4);
+    const int bpc = std::min(k14 ? golk::rule_flip_turn_blocks_per_cu(contig, h->W % 32 != 0, h->birth, h->survive,
+                                                                      h->rule_kernel == 2)
+                                 : golk::flip_turn_blocks_per_cu(contig, h->W % 32 != 0),
+                             4);
     // every block resident at once (with a 10 % margin): block order = blockIdx.
     // Not in a multi-rank ring: its fallback (restore, re-run in ticket order)
     // would redo the batch's exchanges on this rank alone and hang the ring.
@@ -313,7 +322,7 @@ static int flip_stream_locked(golhip_t h, int64_t nturns, int format, void *out,
     // (boards under kFlipStreamMinBlocks blocks keep per-turn launches: their
     // lists are short, and K5r's per-turn waits cost more than a launch;
     // configs[0] through gol.Run measured within noise, profiles/r7u)
-    const bool resident = direct && (h->flip_overlap == 3 || (h->flip_overlap == 2 && nb >= kFlipStreamMinBlocks)) &&
+    const bool resident = !k14 && direct && (h->flip_overlap == 3 || (h->flip_overlap == 2 && nb >= kFlipStreamMinBlocks)) &&
                           coresident && !b.halo && ncopy_r >= 8 &&
                           board_bytes < (1ull << 31) && (uint64_t)dcap * esz < (1ull << 31);
     const int ov = !direct ? 0 : resident ? 2 : std::min(h->flip_overlap, 1);
@@ -742,7 +751,7 @@ int golhip_group_flip_stream(golhip_t *hs, int32_t n, int64_t nturns, int32_t fo
             return fail(GOLHIP_EINVAL, "strip %d is at turn %lld, strip 0 at turn %lld", i, (long long)hs[i]->turns,
                         (long long)hs[0]->turns);
         if (want_il(hs[i]) != want_il(hs[0])) return fail(GOLHIP_EINVAL, "strip %d uses another word layout", i);
-        fused &= hs[i]->local_words() < (1ll << 32) - 4096 && !hs[i]->rule_path();
+        fused &= hs[i]->local_words() < (1ll << 32) - 4096 && hs[i]->fused_flips();
     }
     if (nturns == 0) return GOLHIP_OK;
     // group_exchange's events, made once for the call

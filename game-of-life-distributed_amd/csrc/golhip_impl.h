@@ -46,6 +46,7 @@
 #include "../../include/golhip.h"
 #include "gol_kernels.h"
 #include "gol_rule.h"
+#include "gol_rule_flip.h"
 
 // Internal linkage across units: nothing in namespace gh is a dynamic symbol.
 #define GOLHIP_HIDDEN __attribute__((visibility("hidden")))
@@ -158,6 +159,10 @@ struct golhip {
     int rule_kernel = 0;            // option "rule_kernel" (test hook): 1 a Conway handle on K11 too, 2 K11's dynamic policy always
     bool conway() const { return birth == 0x008 && survive == 0x00C; }
     bool rule_path() const { return !conway() || rule_kernel != 0; }
+    // golhip_set_rule_flips: 1 sends the flip streams of a rule_path() handle through K14 (gol_rule_flip.hip),
+    // one fused launch a turn; 0 (default) through the step kernel and the three-pass compaction
+    int rule_flips = 0;
+    bool fused_flips() const { return !rule_path() || rule_flips == 1; }
     int last_variant = 1;           // kernel family of the last step launch (golhip_perf kernel_variant)
     int skew = 1;                   // option "skew": skewed band stacks (K1w) for per-launch steps
     int skew_young = 0;             // option "skew_young": band height of waves 4..7, % of waves 0..3's (0: by kernel)

@@ -59,4 +59,20 @@ int golhip_rule(golhip_t h, uint32_t *birth, uint32_t *survive) {
     return GOLHIP_OK;
 }
 
+int golhip_set_rule_flips(golhip_t h, int32_t mode) {
+    if (int rc = check(h)) return rc;
+    if (mode != 0 && mode != 1) return fail(GOLHIP_EINVAL, "rule_flips mode %d (0: per turn, 1: fused)", mode);
+    std::lock_guard<std::mutex> g(h->mu);
+    h->rule_flips = mode;
+    return GOLHIP_OK;
+}
+
+int golhip_rule_flips(golhip_t h, int32_t *mode) {
+    if (int rc = check(h)) return rc;
+    if (!mode) return fail(GOLHIP_EINVAL, "null output");
+    std::lock_guard<std::mutex> g(h->mu);
+    *mode = h->rule_flips;
+    return GOLHIP_OK;
+}
+
 }  // extern "C"

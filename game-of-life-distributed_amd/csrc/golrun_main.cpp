@@ -5,6 +5,7 @@
 //          [-viewScale n] [-viewEvery n] [-viewDir dir] [-viewStrips]
 //          [-checkpoint path] [-checkpointEvery n] [-resume path]
 //          [-streamImages] [-imageEvery n] [-blank] [-pattern path@x,y[,op]]... [-saveRle]
+//          [-rule B36/S23] [-ruleFlips]
 //
 // Same flags, defaults and output as main.go: "Threads: / Width: / Height:"
 // lines, then gol.Run on images/<w>x<h>.pgm with an events channel of
@@ -40,7 +41,9 @@
 // an empty board writes none.
 // -rule B36/S23 runs another Life-like rule than Conway's (golhip_rule_parse's
 // spellings; gol_host.h RunOptions::rule); a rule that does not parse ends the
-// run with the parser's message, before any event.
+// run with the parser's message, before any event.  -ruleFlips (or
+// GOL_RULE_FLIPS=1) takes such a run's CellFlipped batches from the fused turn
+// + list kernel (gol_host.h RunOptions::rule_flips); the events are the same.
 // The headless drain loop ends at FinalTurnComplete (main.go:59-66) or when
 // the events channel closes.
 #include <sys/stat.h>
@@ -61,7 +64,7 @@ namespace {
     std::fprintf(stderr, "golrun: %s\nusage: golrun [-t threads] [-w width] [-h height] [-turns n] [-noVis] "
                          "[-root dir] [-device n] [-viewScale n] [-viewEvery n] [-viewDir dir] [-viewStrips] "
                          "[-checkpoint path] [-checkpointEvery n] [-resume path] [-streamImages] [-imageEvery n] [-blank] "
-                         "[-pattern path@x,y[,op]]... [-rule B36/S23] [-saveRle]\n", msg);
+                         "[-pattern path@x,y[,op]]... [-rule B36/S23] [-ruleFlips] [-saveRle]\n", msg);
     std::exit(2);
 }
 
@@ -134,6 +137,8 @@ int main(int argc, char **argv) {
             opt.blank = eq == std::string::npos || val == "true" || val == "1";
         } else if (key == "-saveRle") {
             opt.save_rle = (eq == std::string::npos || val == "true" || val == "1") ? 1 : 0;
+        } else if (key == "-ruleFlips") {
+            opt.rule_flips = (eq == std::string::npos || val == "true" || val == "1") ? 1 : 0;
         } else if (key == "-rule") {
             const std::string text = value();
             if (golhip_rule_parse(text.c_str(), &opt.rule.birth, &opt.rule.survive) != GOLHIP_OK) {

@@ -182,6 +182,8 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "golhip_rule_format": ([u32, u32, ctypes.c_char_p, u64], ctypes.c_int),
         "golhip_set_rule": ([H, u32, u32], ctypes.c_int),
         "golhip_rule": ([H, P(u32), P(u32)], ctypes.c_int),
+        "golhip_set_rule_flips": ([H, i32], ctypes.c_int),
+        "golhip_rule_flips": ([H, P(i32)], ctypes.c_int),
         "golhip_pattern_rule": ([ctypes.c_char_p, P(u32), P(u32)], ctypes.c_int),
         "golhip_comm_unique_id": ([ctypes.c_char_p], ctypes.c_int),
         "golhip_comm_init": ([H, ctypes.c_char_p, i32, i32], ctypes.c_int),
@@ -406,6 +408,18 @@ class Board:
         b, s = ctypes.c_uint32(0), ctypes.c_uint32(0)
         _check(load().golhip_rule(self._h, ctypes.byref(b), ctypes.byref(s)))
         return b.value, s.value
+
+    def set_rule_flips(self, mode: int) -> None:
+        """golhip_set_rule_flips: how flip_stream / step_flips run on a board
+        with another rule than Conway's: 0 (default) a step and a three-pass
+        compaction a turn, 1 the fused turn + list kernel K14.  Same lists."""
+        _check(load().golhip_set_rule_flips(self._h, mode))
+
+    def rule_flips(self) -> int:
+        """golhip_rule_flips: this board's set_rule_flips mode."""
+        m = ctypes.c_int32(0)
+        _check(load().golhip_rule_flips(self._h, ctypes.byref(m)))
+        return m.value
 
     def set_stream(self, stream_ptr: int) -> None:
         _check(load().golhip_set_stream(self._h, ctypes.c_void_p(stream_ptr)))
@@ -675,6 +689,13 @@ def group_set_rule(boards: list[Board], rule) -> None:
     """Board.set_rule on every strip of a group (a group's calls need one rule on all)."""
     for b in boards:
         b.set_rule(rule)
+
+
+def group_set_rule_flips(boards: list[Board], mode: int) -> None:
+    """Board.set_rule_flips on every strip of a group (group_flip_stream runs
+    fused when every strip has mode 1)."""
+    for b in boards:
+        b.set_rule_flips(mode)
 
 
 def group_flip_stream(boards: list[Board], nturns: int, cap: int, fmt: int = FLIPS_XY, out: np.ndarray | None = None):
@@ -1413,6 +1434,7 @@ def stamp_np(board_cells, cells, x0: int, y0: int, op: int = STAMP_COPY) -> np.n
 HOST_LIB_PATH = os.environ.get("GOLHOST_LIB") or os.path.join(HERE, "libgolhost.so")  # A/B builds
 FLAG_KEYS, FLAG_REF_QUIRKS, FLAG_NO_CELL_EVENTS, FLAG_NO_TURN_EVENTS, FLAG_VIEW_STRIPS = 0x1, 0x2, 0x4, 0x8, 0x10
 FLAG_SAVE_RLE = 0x20  # GOLRUN_FLAG_SAVE_RLE
+FLAG_RULE_FLIPS = 0x40  # GOLRUN_FLAG_RULE_FLIPS
 ALIVE_CELLS_COUNT, IMAGE_OUTPUT_COMPLETE, STATE_CHANGE, CELL_FLIPPED, TURN_COMPLETE, FINAL_TURN_COMPLETE = range(6)
 PAUSED, EXECUTING, QUITTING = range(3)
 EVENT_NAMES = ["AliveCellsCount", "ImageOutputComplete", "StateChange", "CellFlipped", "TurnComplete",
@@ -1484,7 +1506,7 @@ class Run:
                  keys: bool = False, quirks: bool = False, cell_events: bool = True, turn_events: bool = True,
                  events_cap: int = 0, ticker_ms: int = 0, view: dict | None = None, checkpoint: dict | None = None,
                  resume: str | None = None, stream_images: bool = False, image_every: int = 0, blank: bool = False,
-                 patterns=None, rule=None, save_rle: bool = False):
+                 patterns=None, rule=None, save_rle: bool = False, rule_flips: bool = False):
         """view: the live view (golrun_start_view), dict(scale=..., every=1,
         x0=0, y0=0, out_w=None, out_h=None, fmt=VIEW_ARGB, strips=False);
         missing out_w / out_h are the largest that fit.  Run.view_frame()
@@ -1506,7 +1528,9 @@ class Run:
         name it or none.  save_rle: beside the final image and the images of
         `s` and `q`, out/<W>x<H>x<turn>.rle with the alive box of the board
         (golhip_save_rle), complete before that image's ImageOutputComplete; an
-        empty board writes none."""
+        empty board writes none.  rule_flips: the CellFlipped events of a run
+        with another rule than Conway's come from the fused turn + list kernel
+        (golhip_set_rule_flips 1 on every handle); the events are the same."""
         lib = load_host()
         rule_word = 0
         if rule is not None:
@@ -1516,7 +1540,7 @@ class Run:
             rule_word = 0 if (rb, rs) == CONWAY else 0x40000 | rs << 9 | rb
         flags = (FLAG_KEYS if keys else 0) | (FLAG_REF_QUIRKS if quirks else 0) | \
             (0 if cell_events else FLAG_NO_CELL_EVENTS) | (0 if turn_events else FLAG_NO_TURN_EVENTS) | \
-            (FLAG_SAVE_RLE if save_rle else 0)
+            (FLAG_SAVE_RLE if save_rle else 0) | (FLAG_RULE_FLIPS if rule_flips else 0)
         more = checkpoint is not None or resume is not None or stream_images or image_every != 0 or blank or \
             bool(patterns) or rule_word != 0  # golrun_start_opts
         spec = None

@@ -279,7 +279,8 @@ int golhip_rule_format(uint32_t birth, uint32_t survive, char *out, uint64_t cap
  * on the rule kernel (K11, canonical words, up to 16 turns a launch; widths
  * that are no multiple of 32 through the padded torus or one turn a launch),
  * never on the resident or skewed kernels, and its flip streams take one turn
- * and one three-pass compaction a turn (same contract).  Every other call
+ * and one three-pass compaction a turn (same contract) unless
+ * golhip_set_rule_flips sends them through the fused kernel.  Every other call
  * works on it unchanged.  The strips of one group must all have the same rule
  * (every call that takes a group: GOLHIP_EINVAL otherwise).
  * Rings: a handle with a communicator (golhip_comm_init, one-rank rings and
@@ -288,6 +289,25 @@ int golhip_rule_format(uint32_t birth, uint32_t survive, char *out, uint64_t cap
  * the ranks of a ring could disagree on the rule and nobody would notice. */
 int golhip_set_rule(golhip_t h, uint32_t birth, uint32_t survive);
 int golhip_rule(golhip_t h, uint32_t *birth, uint32_t *survive);
+/* How golhip_flip_stream and golhip_step_flips run on a handle with another
+ * rule than Conway's.  mode 0 (the default): one step-kernel launch, a
+ * three-pass compaction and two host synchronisations a turn.  mode 1: one
+ * launch a turn of K14, the fused turn + list kernel with the rule as a
+ * policy (a static instance for the named rules, the dynamic policy for every
+ * other), with everything the fused kernel gives Conway: one host round trip
+ * a batch, lists written into golhip_host_alloc memory by the launches' copy
+ * blocks ("flip_overlap" 2 runs as 1: K14 has no resident form), the
+ * co-residency fallback.  Same lists, counts, turns_done and return codes
+ * either way.  Any other value: GOLHIP_EINVAL, nothing changed.  Legal any
+ * time; the board, the turn, the kept count and the flip list stay.  A handle
+ * with Conway's rule keeps its own kernels whatever the mode, and so does a
+ * strip of 2^32 - 4096 words or more its per-turn path.
+ * golhip_group_flip_stream takes the fused per-strip path when every strip of
+ * the group has mode 1 and the per-turn path otherwise.  perf: flip_launches
+ * and flip_entries count K14 as they count Conway's kernel; rule_launches and
+ * step_launches do not move on a mode-1 stream. */
+int golhip_set_rule_flips(golhip_t h, int32_t mode);
+int golhip_rule_flips(golhip_t h, int32_t *mode);
 
 /* ---- multi-GPU -------------------------------------------------------- */
 /* RCCL ring of strips: rank r's neighbours are r-1 (rows above) and r+1

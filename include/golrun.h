@@ -35,6 +35,11 @@ extern "C" {
  * RunOptions::save_rle; the environment's GOL_SAVE_RLE=1 does the same).
  * golrun_opts_t has no free slot left, hence a flag bit. */
 #define GOLRUN_FLAG_SAVE_RLE (1u << 5)
+/* Bit 6, 0x40u: a run with another rule than Conway's takes its CellFlipped
+ * batches from the fused turn + list kernel (golhip_set_rule_flips 1 on every
+ * handle, right after the rule); the events are the same either way (gol_host.h
+ * RunOptions::rule_flips; the environment's GOL_RULE_FLIPS=1 does the same). */
+#define GOLRUN_FLAG_RULE_FLIPS (1u << 6)
 
 /* event kinds (gol/event.go) */
 #define GOLRUN_ALIVE_CELLS_COUNT 0

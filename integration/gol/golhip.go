@@ -126,6 +126,10 @@ package gol
 // static gh_status gh_set_rule(golhip_t h, uint32_t birth, uint32_t survive) {
 //     return gh_wrap(golhip_set_rule(h, birth, survive));
 // }
+// // The flip streams of another rule than Conway's (golhip_set_rule_flips): 0 a
+// // step and a compaction a turn (the default), 1 the fused turn + list kernel.
+// static gh_status gh_set_rule_flips(golhip_t h, int32_t mode) { return gh_wrap(golhip_set_rule_flips(h, mode)); }
+// static gh_status gh_rule_flips(golhip_t h, int32_t *mode) { return gh_wrap(golhip_rule_flips(h, mode)); }
 // // The padded torus (int golhip_set_pad_step(golhip_t h, int32_t mode)): a width
 // // that is no multiple of 32 on the fast kernels; -1 the measured rule (the
 // // default, which the engine keeps), 0 never, 1 always.
@@ -368,8 +372,13 @@ func (e *engine) SetRule(text string) {
 	defer C.free(unsafe.Pointer(ctext))
 	var b, s C.uint32_t
 	check(C.gh_rule_parse(ctext, &b, &s))
+	fused := C.int32_t(0)
+	if envInt("GOL_RULE_FLIPS", 0) != 0 {
+		fused = 1 // the CellFlipped batches from the fused turn + list kernel; the same events
+	}
 	for _, h := range e.hs {
 		check(C.gh_set_rule(h, b, s))
+		check(C.gh_set_rule_flips(h, fused))
 	}
 	e.Rule = [2]uint32{uint32(b), uint32(s)}
 }
