@@ -46,6 +46,22 @@ inline Interval interval(const uint32_t *bits, int64_t n) {
     return {best_start, n - best_gap};
 }
 
+// The same axis on a bounded plane, which has no seam to straddle: the plain
+// interval from the smallest to the largest set position.
+inline Interval interval_plane(const uint32_t *bits, int64_t n) {
+    int64_t first = -1, last = -1;
+    const int64_t nw = (n + 31) / 32;
+    for (int64_t w = 0; w < nw; ++w) {
+        uint32_t v = bits[w];
+        if (w == nw - 1 && (n & 31)) v &= (1u << (n & 31)) - 1u;
+        if (!v) continue;
+        if (first < 0) first = 32 * w + __builtin_ctz(v);
+        last = 32 * w + 31 - __builtin_clz(v);
+    }
+    if (first < 0) return {};
+    return {first, last - first + 1};
+}
+
 // Sets bits [at, at + count) of `dst` from the low `count` bits of `src` words
 // (the rows of one strip appended to the board's row bitmap).
 inline void append_bits(uint32_t *dst, int64_t at, const uint32_t *src, int64_t count) {

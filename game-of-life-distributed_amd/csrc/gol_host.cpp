@@ -202,12 +202,14 @@ struct Engine {
         }
         set_rule(opt);
     }
-    // RunOptions::rule on every handle, before a board is there; right after it RunOptions::rule_flips
+    // RunOptions::rule on every handle, before a board is there; right after it RunOptions::rule_flips and ::plane
     void set_rule(const RunOptions &opt) {
         const bool fused = opt.rule_flips >= 0 ? opt.rule_flips != 0 : env_int("GOL_RULE_FLIPS", 0) != 0;
+        const bool plane = opt.plane >= 0 ? opt.plane != 0 : env_int("GOL_PLANE", 0) != 0;
         for (golhip_t h : hs) {
             check(golhip_set_rule(h, opt.rule.birth, opt.rule.survive));
             check(golhip_set_rule_flips(h, fused ? 1 : 0));
+            check(golhip_set_topology(h, plane ? GOLHIP_TOPOLOGY_PLANE : GOLHIP_TOPOLOGY_TORUS));
         }
     }
     ~Engine() {
@@ -957,6 +959,7 @@ int golrun_start_opts(int64_t turns, int64_t threads, int64_t width, int64_t hei
     if (flags & GOLRUN_FLAG_VIEW_STRIPS) o.view_strips = 1;
     if (flags & GOLRUN_FLAG_SAVE_RLE) o.save_rle = 1;
     if (flags & GOLRUN_FLAG_RULE_FLIPS) o.rule_flips = 1;
+    if (flags & GOLRUN_FLAG_PLANE) o.plane = 1;
     if (view) {
         r->has_view = true;
         o.view = *view;

@@ -479,6 +479,13 @@ struct RunOptions {
     // ignores it.  Opt-in: 1 on, 0 off, -1 from the environment,
     // GOL_RULE_FLIPS=1 (unset: off).
     int rule_flips = -1;
+    // The board as a bounded plane: every cell outside it is dead for ever
+    // (golhip_set_topology GOLHIP_TOPOLOGY_PLANE on every handle and on every
+    // strip of GOL_STRIPS, right after the rule), Golly's "B3/S23:P512,512".
+    // The events are unchanged in kind; a saved RLE names the bounds.  A
+    // checkpoint keeps no topology: a run from resume_path names it again.
+    // Opt-in: 1 on, 0 off, -1 from the environment, GOL_PLANE=1 (unset: off).
+    int plane = -1;
 };
 
 // One "path@x,y[,op]" (op: copy | or | xor | clear, default or), as the

@@ -113,6 +113,17 @@ inline bool rle_header(const char *t, size_t n, Info *info, size_t *body, std::s
         *why = "RLE: no header line \"x = m, y = n[, rule = r]\"";
         return false;
     }
+    // a bounded-grid suffix (":P40,30", ":T100,7") is checked and dropped: a pattern file's bounds are not the board's
+    if (rule.find(':') != std::string::npos) {
+        std::string perr;
+        uint32_t b = 0, s = 0;
+        int topo = 0, bw = 0, bh = 0;
+        if (!golrule::parse_ex(rule.c_str(), &b, &s, &topo, &bw, &bh, &perr)) {
+            *why = "RLE: " + perr;
+            return false;
+        }
+        rule = golrule::strip_bounds(rule);
+    }
     if (!rule.empty() && rm) {
         std::string perr;
         if (!golrule::parse(rule.c_str(), &rm->found_birth, &rm->found_survive, &perr)) {
@@ -303,8 +314,9 @@ class RleWriter {
     ~RleWriter() { abandon(); }
 
     // Opens <path>.tmp and writes the two header lines.  False with *why set; no file is left then.
+    // plane_w, plane_h > 0: the rule carries the bounded-plane suffix ":P<plane_w>,<plane_h>".
     bool open(const char *path, int64_t pw, int64_t ph, uint32_t birth, uint32_t survive, int64_t x0, int64_t y0,
-              int64_t turn, std::string *why) {
+              int64_t turn, std::string *why, int plane_w = 0, int plane_h = 0) {
         path_ = path;
         tmp_ = path_ + ".tmp";
         pw_ = pw;
@@ -316,7 +328,8 @@ class RleWriter {
             return false;
         }
         out_ = "#CXRLE Pos=" + std::to_string(x0) + "," + std::to_string(y0) + " Gen=" + std::to_string(turn) + "\n";
-        out_ += "x = " + std::to_string(pw) + ", y = " + std::to_string(ph) + ", rule = " + golrule::format(birth, survive) + "\n";
+        out_ += "x = " + std::to_string(pw) + ", y = " + std::to_string(ph) + ", rule = " +
+                golrule::format_ex(birth, survive, golrule::kPlane, plane_w, plane_h) + "\n";
         return true;
     }
 

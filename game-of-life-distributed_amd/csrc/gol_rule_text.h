@@ -88,4 +88,72 @@ inline bool parse(const char *text, uint32_t *birth, uint32_t *survive, std::str
     return true;
 }
 
+// Golly's bounded-grid suffix: "<rule>:T<w>,<h>" is a torus, "<rule>:P<w>,<h>"
+// a plane whose outside is dead for ever (the letter in either case, w and h
+// in 1 .. 2^31 - 1; Golly's 0, an infinite dimension, is refused).
+constexpr int kTorus = 0, kPlane = 1;
+
+// parse() with an optional suffix.  Without one: kTorus and bounds 0.
+inline bool parse_ex(const char *text, uint32_t *birth, uint32_t *survive, int *topology, int *bw, int *bh,
+                     std::string *why) {
+    std::string t(text ? text : "");
+    size_t a = 0, e = t.size();
+    while (a < e && is_space(t[a])) ++a;
+    while (e > a && is_space(t[e - 1])) --e;
+    t = t.substr(a, e - a);
+    *topology = kTorus;
+    *bw = *bh = 0;
+    const size_t colon = t.find(':');
+    if (colon == std::string::npos) return parse(t.c_str(), birth, survive, why);
+    auto bad = [&](const std::string &what) {
+        *why = "rule \"" + t + "\": " + what;
+        return false;
+    };
+    const std::string head = t.substr(0, colon);
+    if (!parse(head.c_str(), birth, survive, why)) {
+        // the rule's own fault, under the whole text's name
+        const std::string own = "rule \"" + head + "\": ";
+        return bad(why->compare(0, own.size(), own) == 0 ? why->substr(own.size()) : *why);
+    }
+    size_t p = colon + 1;
+    if (p == t.size()) return bad("nothing after the ':' (expected T<w>,<h> or P<w>,<h>)");
+    const char c = t[p++];
+    if (c == 'T' || c == 't') *topology = kTorus;
+    else if (c == 'P' || c == 'p') *topology = kPlane;
+    else return bad(std::string("topology '") + c + "' (only the torus T<w>,<h> and the plane P<w>,<h> are supported)");
+    int bound[2] = {0, 0};
+    for (int k = 0; k < 2; ++k) {
+        const char *name = k == 0 ? "width" : "height";
+        if (k == 1) {
+            if (p == t.size() || t[p] != ',') return bad("no ',' and height after the width (an infinite dimension is not supported)");
+            ++p;
+        }
+        const size_t d0 = p;
+        uint64_t v = 0;
+        for (; p < t.size() && t[p] >= '0' && t[p] <= '9'; ++p) {
+            v = v * 10 + (uint64_t)(t[p] - '0');
+            if (v > 0x7FFFFFFFull) return bad(std::string("bounded ") + name + " above 2^31 - 1");
+        }
+        if (p == d0) return bad(std::string("no ") + name + " after the topology letter");
+        if (v == 0) return bad(std::string("bounded ") + name + " 0 (an infinite dimension is not supported)");
+        bound[k] = (int)v;
+    }
+    if (p != t.size()) return bad(std::string("character '") + t[p] + "' after the bounds");
+    *bw = bound[0];
+    *bh = bound[1];
+    return true;
+}
+
+// The inverse; with the torus and no bounds, format()'s text.
+inline std::string format_ex(uint32_t birth, uint32_t survive, int topology, int bw, int bh) {
+    std::string s = format(birth, survive);
+    if (bw > 0 && bh > 0)
+        s += std::string(topology == kPlane ? ":P" : ":T") + std::to_string(bw) + "," + std::to_string(bh);
+    return s;
+}
+
+// The rule field with a bounded-grid suffix cut off (a pattern file's bounds
+// are not the board's): the text up to the first ':'.
+inline std::string strip_bounds(const std::string &text) { return text.substr(0, text.find(':')); }
+
 }  // namespace golrule

@@ -109,7 +109,10 @@ int alive_box_locked(golhip_t *hs, int32_t n, Box *box) {
         for (int j = 0; j < Ww; ++j) col[(size_t)j] |= part[(size_t)j];
         golbox::append_bits(row.data(), h->row0, part.data() + Ww, h->rows);
     }
-    const golbox::Interval ix = golbox::interval(col.data(), W), iy = golbox::interval(row.data(), H);
+    // (a bounded plane has no seam: the plain min / max box)
+    const bool plane = hs[0]->plane;
+    const golbox::Interval ix = plane ? golbox::interval_plane(col.data(), W) : golbox::interval(col.data(), W),
+                           iy = plane ? golbox::interval_plane(row.data(), H) : golbox::interval(row.data(), H);
     *box = Box{};
     if (ix.len == 0 || iy.len == 0) return GOLHIP_OK;
     box->x0 = (int32_t)ix.start;
@@ -207,7 +210,10 @@ int golhip_save_rle(golhip_t *hs, int32_t n, const char *path, int32_t x0, int32
     std::vector<uint32_t> words((size_t)(std::min<int64_t>(chunk, ph) * pww));
     golpat::RleWriter w;
     std::string why;
-    if (!w.open(path, pw, ph, hs[0]->birth, hs[0]->survive, x0, y0, turn, &why)) return fail(GOLHIP_EINVAL, "%s", why.c_str());
+    // (a plane handle: "rule = B3/S23:P<W>,<H>", so the file reopens bounded)
+    const bool plane = hs[0]->plane;
+    if (!w.open(path, pw, ph, hs[0]->birth, hs[0]->survive, x0, y0, turn, &why, plane ? hs[0]->W : 0, plane ? hs[0]->H : 0))
+        return fail(GOLHIP_EINVAL, "%s", why.c_str());
     for (int64_t r = 0; r < ph; r += chunk) {
         const int32_t nr = (int32_t)std::min<int64_t>(chunk, ph - r);
         // (w's destructor removes the .tmp file on every early return)

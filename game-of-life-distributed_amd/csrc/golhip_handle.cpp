@@ -601,7 +601,7 @@ int golhip_perf(golhip_t h, golhip_perf_t *out) {
     out->view_kernel_ms = h->ms.view;
     out->pad_launches = n.pad_launches;
     out->rule_launches = n.rule_launches;
-    out->words_per_lane = h->W % 32 == 0 ? wpl_for(h) : 0;
+    out->words_per_lane = (h->W % 32 == 0 || h->plane) ? wpl_for(h) : 0;  // (a plane: K15's one word a lane at any width)
     out->persist_depth = h->W % 32 == 0 ? persist_depth_for(h, wpl_for(h)) : 0;
     return GOLHIP_OK;
 }

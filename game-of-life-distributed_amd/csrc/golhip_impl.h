@@ -23,7 +23,7 @@
 //   golhip_image.cpp    PGM images: the same shadow copy, expanded to bytes in page-locked memory (K9), streamed load
 //   golhip_stamp.cpp    patterns: an empty board, a rectangle of cells stamped on the torus (K10), pattern files
 //   golhip_extract.cpp  saving patterns: any rectangle read back (K12), the alive box (K13), RLE files
-//   golhip_rule.cpp     Life-like rules: their spelling, golhip_set_rule
+//   golhip_rule.cpp     Life-like rules: their spelling, golhip_set_rule; the topology (torus or bounded plane)
 //   golhip_pad.cpp      the padded torus and padded strips: widths that are no multiple of 32 on the fast kernels
 //
 // Everything here but `struct golhip` lives in namespace gh, whose symbols
@@ -47,6 +47,7 @@
 #include "gol_kernels.h"
 #include "gol_rule.h"
 #include "gol_rule_flip.h"
+#include "gol_rule_plane.h"
 
 // Internal linkage across units: nothing in namespace gh is a dynamic symbol.
 #define GOLHIP_HIDDEN __attribute__((visibility("hidden")))
@@ -97,7 +98,7 @@ struct Counters {
     int64_t flip_resident = 0;  // K5r launches (flip_overlap 2)
     int64_t view_frames = 0;    // frames rendered (K7)
     int64_t pad_launches = 0;   // seam refreshes of the padded torus, one per wide launch
-    int64_t rule_launches = 0;  // of step_launches, those on K11
+    int64_t rule_launches = 0;  // of step_launches, those on K11 or (a plane) K15
 };
 // ... and the GOLHIP_FLAG_TIMING sums of the timed spans, by kind (drain_events)
 struct Millis {
@@ -158,11 +159,14 @@ struct golhip {
     uint32_t birth = 0x008, survive = 0x00C;
     int rule_kernel = 0;            // option "rule_kernel" (test hook): 1 a Conway handle on K11 too, 2 K11's dynamic policy always
     bool conway() const { return birth == 0x008 && survive == 0x00C; }
-    bool rule_path() const { return !conway() || rule_kernel != 0; }
+    // golhip_set_topology: a bounded plane (every cell outside the board dead at every turn) steps on K15
+    // (gol_rule_plane.hip), K11's shape at any width and depth; Conway's rule on its static policy there
+    bool plane = false;
+    bool rule_path() const { return !conway() || rule_kernel != 0 || plane; }
     // golhip_set_rule_flips: 1 sends the flip streams of a rule_path() handle through K14 (gol_rule_flip.hip),
     // one fused launch a turn; 0 (default) through the step kernel and the three-pass compaction
     int rule_flips = 0;
-    bool fused_flips() const { return !rule_path() || rule_flips == 1; }
+    bool fused_flips() const { return !plane && (!rule_path() || rule_flips == 1); }  // (K14 has no plane form)
     int last_variant = 1;           // kernel family of the last step launch (golhip_perf kernel_variant)
     int skew = 1;                   // option "skew": skewed band stacks (K1w) for per-launch steps
     int skew_young = 0;             // option "skew_young": band height of waves 4..7, % of waves 0..3's (0: by kernel)

@@ -11,7 +11,8 @@ namespace gh GOLHIP_HIDDEN {
 
 bool pad_applies(golhip_t h) {
     golk::PadPlan p;
-    return h->W % 32 != 0 && h->torus() && !h->ringed() && golk::pad_plan(h->W, &p);
+    // (ghost columns are copies of real ones; a bounded plane has none and runs any width on K15)
+    return h->W % 32 != 0 && h->torus() && !h->ringed() && !h->plane && golk::pad_plan(h->W, &p);
 }
 
 // The measured rule (profiles/widths/bench_widths.json):
@@ -205,7 +206,7 @@ static bool strip_pad_auto(int64_t cells, int64_t nturns) {
 
 static bool pad_group_applies(golhip_t *hs, int32_t n) {
     golk::PadPlan p;
-    if (hs[0]->W % 32 == 0 || !golk::pad_plan(hs[0]->W, &p)) return false;
+    if (hs[0]->W % 32 == 0 || hs[0]->plane || !golk::pad_plan(hs[0]->W, &p)) return false;
     for (int i = 0; i < n; ++i)
         if (hs[i]->ringed()) return false;
     return true;
@@ -309,6 +310,9 @@ int golhip_set_pad_step(golhip_t h, int32_t mode) {
     if (int rc = check(h)) return rc;
     if (mode < -1 || mode > 1) return fail(GOLHIP_EINVAL, "pad step mode %d not in -1..1", mode);
     std::lock_guard<std::mutex> g(h->mu);
+    if (mode == 1 && h->plane)
+        return fail(GOLHIP_EINVAL, "the padded torus copies columns across the row seam: a bounded plane has none "
+                                   "(golhip_set_topology) and steps any width without it");
     if (mode == 1 && !pad_applies(h))
         return fail(GOLHIP_EINVAL, "the padded torus is for a whole torus without a communicator whose width is no "
                                    "multiple of 32 (width %d, rows %d of %d)", h->W, h->rows, h->H);

@@ -217,7 +217,7 @@ int want_il(golhip_t h) { return wpl_for(h) >= 2 ? wpl_for(h) : 0; }
 // Most turns one launch may fuse.  In halo mode the `depth` halo rows must
 // all come from one neighbour strip, so depth <= strip rows.
 int depth_cap(golhip_t h, bool halo) {
-    if (h->W % 32 != 0) return 1;  // generic kernel: one turn per launch
+    if (h->W % 32 != 0 && !h->plane) return 1;  // generic kernel: one turn per launch (a plane has no row seam: K15)
     if (h->rule_path()) {
         // K11's depths (gol_rule.h): every depth depth_plan returns under 16; a
         // cap of exactly 9 would name the quads' own depth
@@ -282,7 +282,8 @@ int rows_per_wave_for(golhip_t h, int depth) {
     int &c = h->auto_rpw[depth_index(depth)];
     if (c == 0 && h->rule_path()) {
         const int slots =
-            h->cu_count * golk::rule_wave_slots_per_cu(depth, h->W, h->birth, h->survive, h->rule_kernel == 2);
+            h->cu_count * (h->plane ? golk::plane_wave_slots_per_cu(depth, h->birth, h->survive, h->rule_kernel == 2)
+                                    : golk::rule_wave_slots_per_cu(depth, h->W, h->birth, h->survive, h->rule_kernel == 2));
         c = golk::auto_rows_per_wave(h->Ww, h->rows, depth, std::max(slots, 1), false, 1, false);
     }
     if (c == 0) {

@@ -107,7 +107,8 @@ static int launch_rows(golhip_t h, int depth, unsigned long long *alive, bool ha
     } else if (h->rows_per_wave > 0) {
         a.rows_per_wave = h->rows_per_wave;
     } else if (rule) {
-        const int slots = h->cu_count * golk::rule_wave_slots_per_cu(depth, h->W, h->birth, h->survive, dyn);
+        const int slots = h->cu_count * (h->plane ? golk::plane_wave_slots_per_cu(depth, h->birth, h->survive, dyn)
+                                                  : golk::rule_wave_slots_per_cu(depth, h->W, h->birth, h->survive, dyn));
         a.rows_per_wave = golk::auto_rows_per_wave(h->Ww, a.rows_out, depth, std::max(slots, 1), false, 1, false);
     } else {
         const int slots = h->cu_count * golk::tb_wave_slots_per_cu(depth, wpl, tb_paired(h));
@@ -121,7 +122,10 @@ static int launch_rows(golhip_t h, int depth, unsigned long long *alive, bool ha
     hipError_t e;
     golk::SkewArgs sk{};
     const bool skew = !rule && skew_plan(h, depth, wpl, a, &sk);
-    if (rule) {
+    if (rule && h->plane) {
+        // K15: the board row of the frame's row 0 (negative in a deep-halo launch of the first strip) and H
+        e = golk::launch_step_plane(a, depth, h->birth, h->survive, h->row0 + lo, h->H, st, dyn);
+    } else if (rule) {
         e = golk::launch_step_rule(a, depth, h->birth, h->survive, st, dyn);
     } else if (skew) {
         sk.base = a;
@@ -131,7 +135,7 @@ static int launch_rows(golhip_t h, int depth, unsigned long long *alive, bool ha
     } else {
         e = golk::launch_step_generic(a, st);
     }
-    h->last_variant = rule ? 5 : h->W % 32 != 0 ? 0 : skew ? 3 : 1;
+    h->last_variant = rule ? (h->plane ? 6 : 5) : h->W % 32 != 0 ? 0 : skew ? 3 : 1;
     if (e != hipSuccess) return fail(GOLHIP_EHIP, "step launch: %s", hipGetErrorString(e));
     if (int rc = span_end(h, 0, true)) return rc;
     h->n.step_launches++;
@@ -529,6 +533,7 @@ int group_check(golhip_t *hs, int32_t n, bool need_board) {
             return fail(GOLHIP_EINVAL, "strip %d does not belong to the group", i);
         if (hs[i]->birth != hs[0]->birth || hs[i]->survive != hs[0]->survive)
             return fail(GOLHIP_EINVAL, "strip %d has another rule than strip 0", i);
+        if (hs[i]->plane != hs[0]->plane) return fail(GOLHIP_EINVAL, "strip %d has another topology than strip 0", i);
         const int expect_row0 = i == 0 ? 0 : hs[i - 1]->row0 + hs[i - 1]->rows;
         if (hs[i]->row0 != expect_row0) return fail(GOLHIP_EINVAL, "strip %d starts at %d, expected %d", i, hs[i]->row0, expect_row0);
     }
@@ -703,6 +708,7 @@ int golhip_comm_init(golhip_t h, const uint8_t id[GOLHIP_UNIQUE_ID_BYTES], int32
     if (int rc = set_dev(h)) return rc;
     if (h->ringed()) return fail(GOLHIP_EINVAL, "comm already initialised");
     if (!h->conway()) return fail(GOLHIP_EINVAL, "a ring runs Conway's B3/S23 only: this handle has another rule (golhip_set_rule)");
+    if (h->plane) return fail(GOLHIP_EINVAL, "a ring runs the torus only: this handle is a bounded plane (golhip_set_topology)");
     if (nranks > 1 && h->rows < 1) return fail(GOLHIP_EINVAL, "empty strip");
     ncclUniqueId u;
     memcpy(&u, id, sizeof u);
@@ -732,6 +738,7 @@ int golhip_test_ring_init(golhip_t h, int32_t nranks, int32_t rank, int32_t ring
     std::lock_guard<std::mutex> g(h->mu);
     if (h->ringed()) return fail(GOLHIP_EINVAL, "comm already initialised");
     if (!h->conway()) return fail(GOLHIP_EINVAL, "a ring runs Conway's B3/S23 only: this handle has another rule (golhip_set_rule)");
+    if (h->plane) return fail(GOLHIP_EINVAL, "a ring runs the torus only: this handle is a bounded plane (golhip_set_topology)");
     if (!h->strip || h->rows < 1 || ring_rows < 1 || ring_rows > h->rows)
         return fail(GOLHIP_EINVAL, "a strip handle and 1 <= ring_rows <= its rows");
     h->xport = fn;

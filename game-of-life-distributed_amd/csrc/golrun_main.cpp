@@ -5,7 +5,7 @@
 //          [-viewScale n] [-viewEvery n] [-viewDir dir] [-viewStrips]
 //          [-checkpoint path] [-checkpointEvery n] [-resume path]
 //          [-streamImages] [-imageEvery n] [-blank] [-pattern path@x,y[,op]]... [-saveRle]
-//          [-rule B36/S23] [-ruleFlips]
+//          [-rule B36/S23[:P<w>,<h>]] [-ruleFlips] [-plane]
 //
 // Same flags, defaults and output as main.go: "Threads: / Width: / Height:"
 // lines, then gol.Run on images/<w>x<h>.pgm with an events channel of
@@ -44,6 +44,13 @@
 // run with the parser's message, before any event.  -ruleFlips (or
 // GOL_RULE_FLIPS=1) takes such a run's CellFlipped batches from the fused turn
 // + list kernel (gol_host.h RunOptions::rule_flips); the events are the same.
+// -plane (or GOL_PLANE=1) runs the board as a bounded plane: every cell outside
+// it is dead for ever (gol_host.h RunOptions::plane).  -rule takes Golly's
+// bounded-grid suffix too: "B3/S23:P512,512" is -plane and "B3/S23:T512,512" the
+// torus, where the bounds equal -w and -h; any other bounds end the run with a
+// message, before any event (a board is as large as its image).  Of several
+// -rule flags the last one counts, suffix included (a later -rule without one
+// is the environment's topology again); -plane or -plane=false wins over a suffix.
 // The headless drain loop ends at FinalTurnComplete (main.go:59-66) or when
 // the events channel closes.
 #include <sys/stat.h>
@@ -64,7 +71,7 @@ namespace {
     std::fprintf(stderr, "golrun: %s\nusage: golrun [-t threads] [-w width] [-h height] [-turns n] [-noVis] "
                          "[-root dir] [-device n] [-viewScale n] [-viewEvery n] [-viewDir dir] [-viewStrips] "
                          "[-checkpoint path] [-checkpointEvery n] [-resume path] [-streamImages] [-imageEvery n] [-blank] "
-                         "[-pattern path@x,y[,op]]... [-rule B36/S23] [-ruleFlips] [-saveRle]\n", msg);
+                         "[-pattern path@x,y[,op]]... [-rule B36/S23[:P<w>,<h>]] [-ruleFlips] [-plane] [-saveRle]\n", msg);
     std::exit(2);
 }
 
@@ -87,6 +94,9 @@ int main(int argc, char **argv) {
     gol::RunOptions opt;
     long long view_scale = 0, view_every = 1;
     std::string view_dir;
+    std::string rule_text;              // -rule's text where it names bounds ...
+    int32_t rule_bw = 0, rule_bh = 0;   // ... and the bounds, held against -w / -h once every flag is read
+    int rule_plane = -1, flag_plane = -1;  // the topology the last -rule's suffix names (-1: none) and -plane's
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         if (a.rfind("--", 0) == 0) a = a.substr(1);  // Go's flag package accepts -flag and --flag
@@ -141,10 +151,17 @@ int main(int argc, char **argv) {
             opt.rule_flips = (eq == std::string::npos || val == "true" || val == "1") ? 1 : 0;
         } else if (key == "-rule") {
             const std::string text = value();
-            if (golhip_rule_parse(text.c_str(), &opt.rule.birth, &opt.rule.survive) != GOLHIP_OK) {
+            int32_t topology = GOLHIP_TOPOLOGY_TORUS;
+            if (golhip_rule_parse_ex(text.c_str(), &opt.rule.birth, &opt.rule.survive, &topology, &rule_bw, &rule_bh) !=
+                GOLHIP_OK) {
                 std::fprintf(stderr, "golrun: %s\n", golhip_last_error());
                 return 1;
             }
+            rule_text = text;
+            // the last -rule alone decides what -rule says of the topology: a text without a suffix says nothing
+            rule_plane = rule_bw > 0 ? (topology == GOLHIP_TOPOLOGY_PLANE ? 1 : 0) : -1;
+        } else if (key == "-plane") {
+            flag_plane = (eq == std::string::npos || val == "true" || val == "1") ? 1 : 0;
         } else if (key == "-pattern") {
             try {
                 opt.patterns.push_back(gol::ParsePattern(value()));
@@ -158,6 +175,12 @@ int main(int argc, char **argv) {
     }
     if (opt.checkpoint_every < 0 || (opt.checkpoint_every > 0 && opt.checkpoint_path.empty()))
         usage("-checkpointEvery must be >= 0 and needs -checkpoint <path>");
+    if (rule_bw > 0 && (rule_bw != params.ImageWidth || rule_bh != params.ImageHeight)) {
+        std::fprintf(stderr, "golrun: rule \"%s\": the bounds %d x %d are not the board's %lld x %lld (-w, -h)\n",
+                     rule_text.c_str(), rule_bw, rule_bh, (long long)params.ImageWidth, (long long)params.ImageHeight);
+        return 1;
+    }
+    opt.plane = flag_plane >= 0 ? flag_plane : rule_plane;  // -plane[=false] wins over a suffix; neither: GOL_PLANE
     params.Turns = turns;  // a Go int (64-bit): the reference's 10^10 default passes through
 
     std::printf("Threads: %lld\nWidth: %lld\nHeight: %lld\n", (long long)params.Threads, (long long)params.ImageWidth,

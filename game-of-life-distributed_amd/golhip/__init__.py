@@ -184,6 +184,10 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "golhip_rule": ([H, P(u32), P(u32)], ctypes.c_int),
         "golhip_set_rule_flips": ([H, i32], ctypes.c_int),
         "golhip_rule_flips": ([H, P(i32)], ctypes.c_int),
+        "golhip_set_topology": ([H, i32], ctypes.c_int),
+        "golhip_topology": ([H, P(i32)], ctypes.c_int),
+        "golhip_rule_parse_ex": ([ctypes.c_char_p, P(u32), P(u32), P(i32), P(i32), P(i32)], ctypes.c_int),
+        "golhip_rule_format_ex": ([u32, u32, i32, i32, i32, ctypes.c_char_p, u64], ctypes.c_int),
         "golhip_pattern_rule": ([ctypes.c_char_p, P(u32), P(u32)], ctypes.c_int),
         "golhip_comm_unique_id": ([ctypes.c_char_p], ctypes.c_int),
         "golhip_comm_init": ([H, ctypes.c_char_p, i32, i32], ctypes.c_int),
@@ -277,6 +281,28 @@ def rule_format(birth: int, survive: int) -> str:
     """golhip_rule_format: the canonical spelling, digits ascending ("B36/S23")."""
     buf = ctypes.create_string_buffer(32)
     _check(load().golhip_rule_format(birth, survive, buf, len(buf)))
+    return buf.value.decode()
+
+
+TOPOLOGY_TORUS = 0  # GOLHIP_TOPOLOGY_*: the board's edges meet (every new board)
+TOPOLOGY_PLANE = 1  # a bounded plane: every cell outside the board is dead for ever
+
+
+def rule_parse_ex(text: str) -> tuple[int, int, int, int, int]:
+    """golhip_rule_parse_ex: rule_parse's spellings with Golly's bounded-grid
+    suffix, "B3/S23:P512,512" (plane) or ":T100,7" (torus) -> (birth, survive,
+    topology, width, height); without a suffix TOPOLOGY_TORUS and bounds 0."""
+    b, s = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    t, w, h = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
+    _check(load().golhip_rule_parse_ex(text.encode(), ctypes.byref(b), ctypes.byref(s), ctypes.byref(t),
+                                       ctypes.byref(w), ctypes.byref(h)))
+    return b.value, s.value, t.value, w.value, h.value
+
+
+def rule_format_ex(birth: int, survive: int, topology: int = TOPOLOGY_TORUS, width: int = 0, height: int = 0) -> str:
+    """golhip_rule_format_ex: the inverse of rule_parse_ex ("B3/S23:P512,512")."""
+    buf = ctypes.create_string_buffer(64)
+    _check(load().golhip_rule_format_ex(birth, survive, topology, width, height, buf, len(buf)))
     return buf.value.decode()
 
 
@@ -420,6 +446,18 @@ class Board:
         m = ctypes.c_int32(0)
         _check(load().golhip_rule_flips(self._h, ctypes.byref(m)))
         return m.value
+
+    def set_topology(self, topology: int) -> None:
+        """golhip_set_topology: TOPOLOGY_TORUS (default) or TOPOLOGY_PLANE, the
+        bounded plane whose outside is dead for ever, for the turns enqueued
+        from now on (any rule, any width, up to 16 turns a launch)."""
+        _check(load().golhip_set_topology(self._h, topology))
+
+    def topology(self) -> int:
+        """golhip_topology: this board's TOPOLOGY_*."""
+        t = ctypes.c_int32(0)
+        _check(load().golhip_topology(self._h, ctypes.byref(t)))
+        return t.value
 
     def set_stream(self, stream_ptr: int) -> None:
         _check(load().golhip_set_stream(self._h, ctypes.c_void_p(stream_ptr)))
@@ -689,6 +727,12 @@ def group_set_rule(boards: list[Board], rule) -> None:
     """Board.set_rule on every strip of a group (a group's calls need one rule on all)."""
     for b in boards:
         b.set_rule(rule)
+
+
+def group_set_topology(boards: list[Board], topology: int) -> None:
+    """Board.set_topology on every strip of a group (a group's calls need one topology on all)."""
+    for b in boards:
+        b.set_topology(topology)
 
 
 def group_set_rule_flips(boards: list[Board], mode: int) -> None:
@@ -1342,6 +1386,20 @@ def life_like_np(cells: np.ndarray, birth: int, survive: int, turns: int = 1) ->
     return a * np.uint8(255)
 
 
+def life_like_plane_np(cells: np.ndarray, birth: int, survive: int, turns: int = 1) -> np.ndarray:
+    """life_like_np on a bounded plane: every cell outside the (H, W) board is
+    dead at every turn (zero padding, no wrap)."""
+    a = (np.asarray(cells) == 255).astype(np.uint8)
+    bt = np.array([(birth >> n) & 1 for n in range(9)], dtype=np.uint8)
+    st = np.array([(survive >> n) & 1 for n in range(9)], dtype=np.uint8)
+    for _ in range(turns):
+        p = np.pad(a, 1)
+        rows = p[:-2, :] + p[1:-1, :] + p[2:, :]
+        n = rows[:, :-2] + rows[:, 1:-1] + rows[:, 2:] - a
+        a = np.where(a == 1, st[n], bt[n]).astype(np.uint8)
+    return a * np.uint8(255)
+
+
 def rle_parse_np(text: str) -> np.ndarray:
     """The cells of RLE text as a (y, x) bool array.  Raises ValueError where
     the library refuses the file."""
@@ -1353,7 +1411,7 @@ def rle_parse_np(text: str) -> np.ndarray:
     if not head:
         raise ValueError("no header")
     w, h, rule = int(head.group(1)), int(head.group(2)), head.group(3)
-    if rule is not None and rule.upper() not in ("B3/S23", "23/3"):
+    if rule is not None and re.fullmatch(r"(.*?)(:[TtPp][1-9]\d*,[1-9]\d*)?", rule).group(1).upper() not in ("B3/S23", "23/3"):
         raise ValueError("rule")
     if not (1 <= w < 2 ** 31 and 1 <= h < 2 ** 31):
         raise ValueError("size")
@@ -1435,6 +1493,7 @@ HOST_LIB_PATH = os.environ.get("GOLHOST_LIB") or os.path.join(HERE, "libgolhost.
 FLAG_KEYS, FLAG_REF_QUIRKS, FLAG_NO_CELL_EVENTS, FLAG_NO_TURN_EVENTS, FLAG_VIEW_STRIPS = 0x1, 0x2, 0x4, 0x8, 0x10
 FLAG_SAVE_RLE = 0x20  # GOLRUN_FLAG_SAVE_RLE
 FLAG_RULE_FLIPS = 0x40  # GOLRUN_FLAG_RULE_FLIPS
+FLAG_PLANE = 0x80  # GOLRUN_FLAG_PLANE
 ALIVE_CELLS_COUNT, IMAGE_OUTPUT_COMPLETE, STATE_CHANGE, CELL_FLIPPED, TURN_COMPLETE, FINAL_TURN_COMPLETE = range(6)
 PAUSED, EXECUTING, QUITTING = range(3)
 EVENT_NAMES = ["AliveCellsCount", "ImageOutputComplete", "StateChange", "CellFlipped", "TurnComplete",
@@ -1506,7 +1565,7 @@ class Run:
                  keys: bool = False, quirks: bool = False, cell_events: bool = True, turn_events: bool = True,
                  events_cap: int = 0, ticker_ms: int = 0, view: dict | None = None, checkpoint: dict | None = None,
                  resume: str | None = None, stream_images: bool = False, image_every: int = 0, blank: bool = False,
-                 patterns=None, rule=None, save_rle: bool = False, rule_flips: bool = False):
+                 patterns=None, rule=None, save_rle: bool = False, rule_flips: bool = False, plane: bool = False):
         """view: the live view (golrun_start_view), dict(scale=..., every=1,
         x0=0, y0=0, out_w=None, out_h=None, fmt=VIEW_ARGB, strips=False);
         missing out_w / out_h are the largest that fit.  Run.view_frame()
@@ -1530,7 +1589,9 @@ class Run:
         (golhip_save_rle), complete before that image's ImageOutputComplete; an
         empty board writes none.  rule_flips: the CellFlipped events of a run
         with another rule than Conway's come from the fused turn + list kernel
-        (golhip_set_rule_flips 1 on every handle); the events are the same."""
+        (golhip_set_rule_flips 1 on every handle); the events are the same.
+        plane: the board is a bounded plane, every cell outside it dead for ever
+        (golhip_set_topology on every handle and strip); same kinds of events."""
         lib = load_host()
         rule_word = 0
         if rule is not None:
@@ -1540,7 +1601,8 @@ class Run:
             rule_word = 0 if (rb, rs) == CONWAY else 0x40000 | rs << 9 | rb
         flags = (FLAG_KEYS if keys else 0) | (FLAG_REF_QUIRKS if quirks else 0) | \
             (0 if cell_events else FLAG_NO_CELL_EVENTS) | (0 if turn_events else FLAG_NO_TURN_EVENTS) | \
-            (FLAG_SAVE_RLE if save_rle else 0) | (FLAG_RULE_FLIPS if rule_flips else 0)
+            (FLAG_SAVE_RLE if save_rle else 0) | (FLAG_RULE_FLIPS if rule_flips else 0) | \
+            (FLAG_PLANE if plane else 0)
         more = checkpoint is not None or resume is not None or stream_images or image_every != 0 or blank or \
             bool(patterns) or rule_word != 0  # golrun_start_opts
         spec = None

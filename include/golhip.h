@@ -93,9 +93,11 @@ typedef struct golhip_perf {
     int32_t rows_per_wave;    /* rows streamed per wavefront (full-depth launch)*/
     int32_t kernel_variant;   /* 0 = generic (width % 32 != 0), 1 = bit-sliced, 3 = skewed
                                  band stacks, 4 = resident LDS bands, 5 = the rule kernel
-                                 (K11, golhip_set_rule; any width); after a padded step:
-                                 the wide board's                             */
-    int32_t words_per_lane;   /* 1, 2 (interleaved pairs) or 4 (quads); 0 generic */
+                                 (K11, golhip_set_rule; any width), 6 = the plane kernel
+                                 (K15, golhip_set_topology; any width); after a padded
+                                 step: the wide board's                       */
+    int32_t words_per_lane;   /* 1, 2 (interleaved pairs) or 4 (quads); 0 generic
+                                 (width % 32 != 0 off the plane kernel)       */
     int64_t persist_fallbacks; /* resident launches that timed out (not all workgroups
                                   co-resident) and were re-run on per-launch kernels */
     int64_t flip_launches;    /* fused turn + flip-list kernels (one turn each)  */
@@ -114,8 +116,8 @@ typedef struct golhip_perf {
     int64_t halo_exchanges;   /* halo exchanges posted (RCCL ring)               */
     double halo_ms;           /* their summed time on the stream they ran on
                                  (GOLHIP_FLAG_TIMING)                           */
-    int64_t rule_launches;    /* of step_launches, those on the rule kernel (K11,
-                                 kernel_variant 5; the offset of the retired
+    int64_t rule_launches;    /* of step_launches, those on the rule kernels (K11,
+                                 kernel_variant 5; K15 on a plane, 6; the offset of the retired
                                  overlap_launches / reserved2)                   */
     int64_t skew_half_launches; /* of skew_launches, those on half-wave tiles    */
     int64_t lds_launches;     /* of persist_launches, those that ran resident LDS
@@ -308,6 +310,52 @@ int golhip_rule(golhip_t h, uint32_t *birth, uint32_t *survive);
  * step_launches do not move on a mode-1 stream. */
 int golhip_set_rule_flips(golhip_t h, int32_t mode);
 int golhip_rule_flips(golhip_t h, int32_t *mode);
+
+/* ---- Topology: torus or bounded plane ---------------------------------- */
+/* GOLHIP_TOPOLOGY_TORUS (the default of every new handle): the board's edges
+ * meet, as everywhere above.  GOLHIP_TOPOLOGY_PLANE: Golly's bounded plane
+ * "B3/S23:P512,512": every cell outside [0, W) x [0, H) is dead for ever, at
+ * every turn.  A margin of dead cells cannot give that (a cell born in the
+ * margin feeds the board's edge a turn later), so a plane handle steps on K15,
+ * the rule kernel with the outside forced dead inside every fused turn: any
+ * rule (Conway's on its static policy), ANY width at up to 16 turns a launch
+ * on canonical words (a plane has no row seam: no padded torus, pad_launches
+ * stays 0), never on the resident or skewed kernels.  perf: kernel_variant 6;
+ * its launches count in rule_launches.
+ * golhip_set_topology: any time on a handle without a communicator (a handle
+ * with one, golhip_test_ring_init's included, refuses the plane; the torus is
+ * always accepted); the board, the turn, the kept count and the flip list
+ * stay, and the turns enqueued from now on run on the new topology.  A handle
+ * with golhip_set_pad_step 1 refuses the plane, and a plane handle refuses
+ * golhip_set_pad_step 1 (ghost columns are copies; a plane has none).  The
+ * flip streams of a plane handle take the per-turn path (one K15 turn and one
+ * three-pass compaction a turn) whatever golhip_set_rule_flips says: same
+ * lists, counts and return codes.  The strips of one group must all have the
+ * same topology (every call that takes a group: GOLHIP_EINVAL otherwise).
+ * Count, hash, view, image, checkpoint, stamp and extract do not look at the
+ * topology (a stamp or an extract that crosses an edge still wraps);
+ * golhip_alive_box returns the plain min / max box on a plane handle, and
+ * golhip_save_rle on one writes "rule = <B/S>:P<W>,<H>", so the file reopens
+ * bounded (golhip_pattern_write takes no handle and writes the plain rule).
+ * A checkpoint keeps no topology, as it keeps no rule: a resume sets it again. */
+#define GOLHIP_TOPOLOGY_TORUS 0
+#define GOLHIP_TOPOLOGY_PLANE 1
+int golhip_set_topology(golhip_t h, int32_t topology);
+int golhip_topology(golhip_t h, int32_t *topology);
+/* golhip_rule_parse with Golly's bounded-grid suffix: what golhip_rule_parse
+ * takes, then optionally ":T<w>,<h>" (torus) or ":P<w>,<h>" (plane), the letter
+ * in either case, w and h in 1 .. 2^31 - 1.  Without a suffix *topology is
+ * GOLHIP_TOPOLOGY_TORUS and both bounds are 0.  A bound of 0 (Golly's infinite
+ * dimension), a missing bound, another topology letter or anything behind the
+ * bounds is GOLHIP_EINVAL with a message naming the fault.  golhip_rule_parse
+ * itself goes on refusing the suffix.
+ * golhip_rule_format_ex is the inverse: "B3/S23:P512,512"; with both bounds 0
+ * and the torus, golhip_rule_format's text.  GOLHIP_EINVAL for a plane without
+ * bounds, one bound of 0, a negative bound or another topology. */
+int golhip_rule_parse_ex(const char *text, uint32_t *birth, uint32_t *survive, int32_t *topology, int32_t *bw,
+                         int32_t *bh);
+int golhip_rule_format_ex(uint32_t birth, uint32_t survive, int32_t topology, int32_t bw, int32_t bh, char *out,
+                          uint64_t cap);
 
 /* ---- multi-GPU -------------------------------------------------------- */
 /* RCCL ring of strips: rank r's neighbours are r-1 (rows above) and r+1

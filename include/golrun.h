@@ -40,6 +40,11 @@ extern "C" {
  * handle, right after the rule); the events are the same either way (gol_host.h
  * RunOptions::rule_flips; the environment's GOL_RULE_FLIPS=1 does the same). */
 #define GOLRUN_FLAG_RULE_FLIPS (1u << 6)
+/* Bit 7, 0x80u: the run's board is a bounded plane, every cell outside it dead
+ * for ever (golhip_set_topology GOLHIP_TOPOLOGY_PLANE on every handle, strips
+ * included, right after the rule); the events are unchanged in kind (gol_host.h
+ * RunOptions::plane; the environment's GOL_PLANE=1 does the same). */
+#define GOLRUN_FLAG_PLANE (1u << 7)
 
 /* event kinds (gol/event.go) */
 #define GOLRUN_ALIVE_CELLS_COUNT 0
